@@ -16,6 +16,18 @@ words, exact carrier planner) and the proofs (on the GPU: gss_linearize_device) 
 timed region (host_plan_s, host_linearize_s), each rank planning only its own window
 (gpssim_amd/shard.py).
 
+A plain run (bench.py --gpus 1 --steps N --warmup W) does only what the headline needs: it plans
+and proves the window, warms up, times the N steps, writes the outputs if --dump-outputs DIR is
+given, and prints the JSON line.  Every other leg below (cpu_baseline, exact_path, window,
+per_config, e2e, gather, the sustained-clock launches and the live PMC traffic passes) runs only
+with --full; there the --no-* options switch single legs off, and each leg times the headline's
+steps and warm-up up to --leg-steps and --leg-warmup (20 and 5), so that a full run stays within
+minutes whatever --steps is.  Without --full their fields are null.
+
+--dump-outputs DIR: after the timed steps, what the last timed step left in HBM (the rank's -b
+byte stream, DeviceWindow.out) goes to DIR as .npy files (dump_outputs); the scenario is
+deterministic, so two builds run with the same arguments can be compared file for file.
+
 Extra JSON fields besides the driver contract:
   x_realtime, stages_ms, host_plan_s, host_linearize_s (max over ranks), lib (the library that
   was measured);
@@ -255,6 +267,7 @@ def lib_sha16(path):
         return hashlib.sha256(f.read()).hexdigest()[:16]
 
 
+LEG_STEPS, LEG_WARMUP = 20, 5  # --full: the other legs' cap on the headline's steps and warm-up
 PROFILE_TOL = 0.10     # a profile's kernel time must be within 10 % of the un-profiled run's
 
 
@@ -363,6 +376,50 @@ def live_traffic(fmt, window, threads, kern_ms, steps, warmup, timeout=150):
     finally:
         if not save:
             shutil.rmtree(top, ignore_errors=True)
+
+
+DUMP_SAMPLE_VALUES = 12 << 20  # float32 values of the sampled blocks: 48 MiB of the 64 MB allowed
+DUMP_SEED = 0
+
+
+def dump_outputs(torch, res, fmt, path, tag=""):
+    """The window's rendered byte stream (res.out, as the last step left it) as .npy files in
+    `path` (`tag` separates the ranks of a multi-GPU run):
+      block_checksums.npy    float64 [nblk, 2], over every byte of the output: per block the sum
+                             of its bytes and the sum of byte * (1 + offset mod 251), both exact
+                             in float64 (below 2^53 for blocks up to 8 MB);
+      iq_sample_blocks.npy   float64 [k]: the sampled blocks, the first and the last block and a
+                             seeded choice (DUMP_SEED) of the others, ascending;
+      iq_sample.npy          float32 [k, values per block]: those blocks' whole contents, the
+                             I/Q values of -b 16 (int16) and -b 8 (int8), the packed bytes of
+                             -b 1."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    nblk, bb = res.nblk, res.bb
+    out = res.out[:nblk * bb].view(nblk, bb)
+    weight = torch.arange(bb, device=out.device, dtype=torch.int64) % 251 + 1
+    sums = np.zeros((nblk, 2), np.float64)
+    rows = max(1, (64 << 20) // bb)
+    for b0 in range(0, nblk, rows):
+        part = out[b0:b0 + rows].to(torch.int64)
+        sums[b0:b0 + len(part), 0] = part.sum(1).cpu().numpy()
+        sums[b0:b0 + len(part), 1] = (part * weight).sum(1).cpu().numpy()
+    per_block = bb // 2 if fmt == 16 else bb
+    k = max(1, min(nblk, DUMP_SAMPLE_VALUES // per_block))
+    if k >= nblk:
+        idx = np.arange(nblk, dtype=np.int64)
+    else:
+        ends = [0, nblk - 1][:k]
+        rest = np.random.default_rng(DUMP_SEED).permutation(np.arange(1, nblk - 1))
+        idx = np.sort(np.concatenate([ends, rest[:k - len(ends)]])).astype(np.int64)
+    raw = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    vals = raw.view({16: "<i2", 8: "i1"}.get(fmt, "u1")).astype(np.float32)
+    for name, a in (("block_checksums", sums), ("iq_sample_blocks", idx.astype(np.float64)),
+                    ("iq_sample", vals)):
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
+    return {"dir": path, "files": [f"{n}{tag}.npy" for n in ("block_checksums",
+                                                              "iq_sample_blocks", "iq_sample")],
+            "bytes": int(sums.nbytes + idx.size * 8 + vals.nbytes), "sampled_blocks": int(k)}
 
 
 def time_steps(torch, dev, dev_t, res, steps, warmup, stream):
@@ -793,6 +850,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--window", type=float, default=WINDOW_S, help="seconds per GPU")
     ap.add_argument("--fmt", type=int, default=16, choices=[1, 8, 16])
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline (cpu_baseline, exact_path, "
+                         "window, per_config, e2e, gather, sustained clock, live PMC traffic); "
+                         "the --no-* options below then switch single legs off")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step rendered to DIR as .npy files "
+                         "(dump_outputs)")
+    ap.add_argument("--leg-steps", type=int, default=LEG_STEPS,
+                    help="--full: the other legs time min(--steps, this) steps each, so that "
+                         "a long headline run does not multiply their time")
+    ap.add_argument("--leg-warmup", type=int, default=LEG_WARMUP,
+                    help="--full: the other legs warm up min(--warmup, this) steps each")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact", action="store_true",
                     help="skip the exact-path run on the same batch (exact_path)")
@@ -817,6 +886,15 @@ def main():
     ap.add_argument("--gather-window", type=float, default=GATHER_WINDOW_S,
                     help="seconds per rank of the gather leg's 20 MS/s run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.leg_steps < 1 or args.leg_warmup < 0:
+        ap.error("--steps and --leg-steps must be at least 1, the warm-ups at least 0")
+    # the legs besides the headline: its steps and warm-up up to a cap (configs[4] alone takes
+    # 0.4 s per step, and the live PMC passes rerun the steps three times under the profiler)
+    leg_steps, leg_warmup = min(args.steps, args.leg_steps), min(args.warmup, args.leg_warmup)
+    if not args.full:                 # a plain run: the headline alone
+        for leg in ("cpu_baseline", "exact", "configs", "window", "e2e", "sustained", "pmc",
+                    "gather"):
+            setattr(args, "no_" + leg, True)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -902,6 +980,11 @@ def main():
     n_launch, ck_ms, syn_ms = dev.timing()
     n_lin, lin_ms = dev.timing_lin()
     host_lin_s = res.lin_s
+    dumped = None
+    if args.dump_outputs:             # the last timed step's output, before any other leg runs
+        dumped = dump_outputs(torch, res, args.fmt, args.dump_outputs,
+                              tag=f"_rank{rank}" if dist else "")
+        progress(f"dumped {dumped['bytes']} bytes to {args.dump_outputs}")
     # informational, after the timed region: the same launches continued until the shader clock
     # has finished ramping (clock ramp), i.e. the rate of a long run
     sustained_ms = None
@@ -910,7 +993,7 @@ def main():
             res.step(stream)
         torch.cuda.synchronize(dev_t)
         dev.timing_reset()
-        for _ in range(args.steps):
+        for _ in range(leg_steps):
             res.step(stream)
         torch.cuda.synchronize(dev_t)
         sustained_ms = round(dev.timing_lin()[1], 3)
@@ -946,19 +1029,19 @@ def main():
     if single and not args.no_exact:
         # the same resident batch through the exact path alone (Stage A + Stage B for every
         # block, no host-side line proofs), timed the same way
-        for _ in range(args.warmup):
+        for _ in range(leg_warmup):
             step_serial()
         torch.cuda.synchronize(dev_t)
         t1 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(leg_steps):
             step_serial()
         torch.cuda.synchronize(dev_t)
         el = time.perf_counter() - t1
-        exact = {"value": round(samples_rank * args.steps / el / 1e6, 2),
-                 "ms_per_step": round(el / args.steps * 1e3, 3)}
+        exact = {"value": round(samples_rank * leg_steps / el / 1e6, 2),
+                 "ms_per_step": round(el / leg_steps * 1e3, 3), "steps": leg_steps}
     window = None
     if single and not args.no_window and res.proof == "gpu":
-        window = window_leg(torch, dev, dev_t, res, args.steps, args.warmup, stream, exact,
+        window = window_leg(torch, dev, dev_t, res, leg_steps, leg_warmup, stream, exact,
                             anch=plan_t.get("anch"), heads=plan_t.get("spec_heads"))
         progress(f"window (proof + render): {window['value']} MS/s, proof {window['proof_ms']} ms")
     ms_per_step = elapsed / args.steps * 1e3
@@ -992,13 +1075,13 @@ def main():
     if single and not args.no_configs:
         # the headline's steps and warm-up: the shader clock ramps over the first ~25 launches
         # after an idle spell, so a leg timed on fewer launches reads slower
-        configs = per_config(G, torch, dev, dev_t, stream, args.steps, args.warmup, args.threads,
+        configs = per_config(G, torch, dev, dev_t, stream, leg_steps, leg_warmup, args.threads,
                              e2e=not args.no_e2e)
     # the live PMC passes last: their processes' device memory is wiped when they exit (above)
-    traffic, traffic_src, prof = None, "not measured (--no-pmc)", None
+    traffic, traffic_src, prof = None, "not measured (a run without --full, or --no-pmc)", None
     if single and not args.no_pmc:
         traffic, traffic_src, prof = live_traffic(args.fmt, args.window, args.threads, lin_ms,
-                                                  args.steps, args.warmup)
+                                                  leg_steps, leg_warmup)
     if traffic is None:
         t2, s2 = load_traffic(workload, "gss_lin_kernel", lin_ms, sha)
         if t2 is not None:
@@ -1045,6 +1128,10 @@ def main():
         "e2e": e2e,
         "exact_path": exact,
         "window": window,
+        "full": args.full,
+        "leg_steps": leg_steps if args.full else None,
+        "leg_warmup": leg_warmup if args.full else None,
+        "dumped_outputs": dumped,
         "lib": {"path": os.path.relpath(G.LIB_PATH, REPO), "version": version, "sha16": sha},
     }
     if rank == 0:

@@ -1,7 +1,8 @@
 """bench.py pieces that need no GPU: the metric is BASELINE.json's, the committed PMC traffic
 record (profiles/pmc_traffic.json) is attached only to the workload, kernel and library build it
 was measured on and only when its kernel time agrees with its own run's events, and the CPU
-baseline runs the reference binary pinned per core without a launcher hop."""
+baseline runs the reference binary pinned per core without a launcher hop; --dump-outputs writes
+the rendered window as float arrays (dump_outputs), and one GPU test runs a plain bench."""
 import json
 import os
 import sys
@@ -59,6 +60,98 @@ def test_dtype_label_follows_the_build():
     assert info["lin_mfma"] in ("0", "1", "2")
     assert G.lib_mfma() == (info["lin_mfma"] != "0")
     assert info["lin_mfma"] == "2"                 # the shipped build: channel pairs on MFMA
+
+
+@pytest.mark.parametrize("fmt,nblk,bb,cap", [(16, 7, 4000, None), (8, 5, 2002, None),
+                                              (1, 3, 251, None), (16, 40, 4000, 5 * 2000 + 7),
+                                              (8, 9, 300, 2 * 300), (16, 1, 64, None)])
+def test_dump_outputs_files(tmp_path, monkeypatch, fmt, nblk, bb, cap):
+    """--dump-outputs: checksums over every block, the whole contents of the sampled blocks (all
+    of them while they fit, else the first, the last and a seeded choice), float arrays of at
+    most 64 MB, the same on every call"""
+    import numpy as np
+    import torch
+    from types import SimpleNamespace
+    if cap is not None:                # fewer values than the window holds: a sample
+        monkeypatch.setattr(bench, "DUMP_SAMPLE_VALUES", cap)
+    raw = np.random.default_rng(fmt + nblk).integers(0, 256, nblk * bb + 5, dtype=np.uint8)
+    res = SimpleNamespace(nblk=nblk, bb=bb, out=torch.from_numpy(raw.copy()))
+    info = bench.dump_outputs(torch, res, fmt, str(tmp_path / "a"))
+    bench.dump_outputs(torch, res, fmt, str(tmp_path / "b"), tag="_rank1")
+    got = {n: np.load(tmp_path / "a" / n) for n in info["files"]}
+    assert sorted(info["files"]) == sorted(os.listdir(tmp_path / "a"))
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) == info["bytes"] <= 64e6
+    for n, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / n.replace(".npy", "_rank1.npy")))
+    blocks = raw[:nblk * bb].reshape(nblk, bb).astype(np.int64)
+    w = np.arange(bb) % 251 + 1
+    want = np.stack([blocks.sum(1), (blocks * w).sum(1)], 1)
+    assert np.array_equal(got["block_checksums.npy"], want.astype(np.float64))
+    idx = got["iq_sample_blocks.npy"].astype(np.int64)
+    assert idx[0] == 0 and idx[-1] == nblk - 1 and np.all(np.diff(idx) > 0)
+    assert len(idx) == info["sampled_blocks"] == min(nblk, bench.DUMP_SAMPLE_VALUES //
+                                                     (bb // 2 if fmt == 16 else bb))
+    view = {16: "<i2", 8: "i1", 1: "u1"}[fmt]
+    sample = got["iq_sample.npy"]
+    assert np.array_equal(sample, raw[:nblk * bb].reshape(nblk, bb)[idx].view(view)
+                          .astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone(tmp_path, golden):
+    """a plain run (no --full) times --steps steps, reports ms_per_step, leaves every other leg
+    out, and its --dump-outputs sample holds the reference's blocks (golden block hashes of the
+    same static scenario)"""
+    import hashlib
+    import subprocess
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps",
+                        "3", "--warmup", "1", "--window", "3", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["metric"] == bench.METRIC and d["unit"] == "MS/s" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["stages_ms"]["launches_timed"] == 3
+    assert d["ms_per_step"] > 0
+    # value and ms_per_step are the same timing (both rounded to their last printed digit)
+    assert abs(d["ms_per_step"] - 29 * 260000 / (d["value"] * 1e3)) <= 0.001
+    for leg in ("cpu_baseline", "per_config", "gather", "e2e", "exact_path", "window"):
+        assert d[leg] is None, leg
+    assert d["stages_ms"]["fast_path_sustained"] is None and d["roofline"]["profile"] is None
+    assert sorted(d["dumped_outputs"]["files"]) == sorted(os.listdir(out))
+    idx = np.load(out / "iq_sample_blocks.npy").astype(int)
+    sample = np.load(out / "iq_sample.npy")
+    sums = np.load(out / "block_checksums.npy")
+    assert sums.shape == (29, 2) and sample.shape == (len(idx), 2 * 260000) and idx[0] == 0
+    want = golden["static_d30_b16"]["block_sha16"]
+    for i, b in enumerate(idx):
+        raw = sample[i].astype("<i2").tobytes()
+        assert hashlib.sha256(raw).hexdigest()[:16] == want[b], b
+        assert np.frombuffer(raw, np.uint8).sum() == sums[b, 0]
+
+
+@pytest.mark.gpu
+def test_full_run_caps_the_other_legs_steps():
+    """--full with a longer headline (--steps 100, within the library's ring of 256 timed
+    launches that launches_timed counts): the headline times all 100, the other legs the
+    capped 20 after 5 warm-up steps (here exact_path, window and the sustained launches on a 3 s
+    window; the process-starting and long legs off)"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "1",
+                        "--steps", "100", "--warmup", "7", "--window", "3", "--no-cpu-baseline",
+                        "--no-e2e", "--no-configs", "--no-pmc"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["full"] is True and d["steps"] == 100 and d["warmup"] == 7
+    assert d["stages_ms"]["launches_timed"] == 100
+    assert d["leg_steps"] == bench.LEG_STEPS == 20 and d["leg_warmup"] == bench.LEG_WARMUP == 5
+    assert d["exact_path"]["steps"] == 20 and d["exact_path"]["value"] > 0
+    assert d["window"]["steps"] == 20 and d["window"]["warmup"] == 5
+    assert d["stages_ms"]["fast_path_sustained"] > 0
 
 
 def test_step_issue_efficiency_bounds():

@@ -7,7 +7,7 @@
 #
 # steps:
 #   tests            pytest -m gpu (whole suite)          quick   the fast-path + parity GPU tests
-#   smoke            __graft_entry__.smoke()              bench   bench.py as the driver runs it
+#   smoke            __graft_entry__.smoke()              bench   bench.py --full (every leg)
 #   ablate:V1,V2,..  kernel time of the current build and _var/<Vi> (tools/ablate.sh builds),
 #                    interleaved ROUNDS (default 2) times, bench.py --no-* legs off
 #   clock:V1,V2,..   in-kernel clock stamps of _var/<Vi> (LIN_STAMP builds), interleaved ROUNDS
@@ -48,7 +48,7 @@ for s in "$@"; do
         timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
         step smoke $? ;;
     bench)
-        timeout -k 10 600 python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
+        timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
         step bench $? ;;
     ablate:*)
         vs=${s#ablate:}
@@ -82,7 +82,7 @@ for s in "$@"; do
                 lib=gps-sdr-sim_amd/lib/libgpssim_amd.so
                 [ "$v" != cur ] && lib=_var/$v/libgpssim_amd.so
                 line=$(GSS_ALLOW_LIB_OVERRIDE=1 GSS_LIB_PATH=$lib timeout -k 10 200 python bench.py \
-                    --steps 1 --warmup 0 --no-cpu-baseline --no-exact --no-configs --no-pmc \
+                    --full --steps 1 --warmup 0 --no-cpu-baseline --no-exact --no-configs --no-pmc \
                     --no-sustained 2>>$OUT/e2eab.err | tail -1)
                 step "e2eab $v" $?
                 echo "$v $(echo "$line" | python3 -c 'import json,sys; d=json.load(sys.stdin)["e2e"]; print(d["value"], d["d2h_GBps"], d["frac_of_d2h_ceiling"], d.get("steady_frac_of_d2h_ceiling"))')" >> $OUT/e2eab.log
@@ -92,7 +92,7 @@ for s in "$@"; do
         a=${s#rehearse:}; n=${a%%:*}; t=""; [ "$a" != "$n" ] && t=_${a#*:}
         GSS_BENCH_REHEARSE=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 \
             --nproc-per-node $n --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $n \
-            ${REHEARSE_ARGS:---steps 3 --warmup 1 --no-pmc} > $OUT/rehearse$n$t.json \
+            ${REHEARSE_ARGS:---full --steps 3 --warmup 1 --no-pmc} > $OUT/rehearse$n$t.json \
             2> $OUT/rehearse$n$t.err
         step "rehearse $n$t" $? ;;
     pmcclk:*)

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Apply INTEGRATION.md §2 to a /tmp copy of the reference's gpssim.c and build it.
+"""Apply INTEGRATION.md §2 to a scratch copy of the reference's gpssim.c and build it.
 
-The reference stays untouched (/root/reference is read-only); its gpssim.c and gpssim.h are
-copied to /tmp/gss_integ/ and edited there:
+The reference stays untouched; its gpssim.c and gpssim.h are copied to a temporary directory
+(removed afterwards) and edited there:
   1. two prototypes after `#include "gpssim.h"`;
   2. the sample loop and its pack/fwrite epilogue (gpssim.c:2190-2288: from
      `for (isamp=0; isamp<iq_buff_size; isamp++)` through the SC16 fwrite branch) become
@@ -21,11 +21,11 @@ import re
 import shutil
 import subprocess
 import sys
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference"
-WORK = "/tmp/gss_integ"
 OUT = os.path.join(REPO, "oracle", "_ref", "gps-sdr-sim-integ")
 OUT_INT = OUT + "-intcarr"
 
@@ -71,8 +71,13 @@ def build(work, out, drop_float_carr):
 def main():
     if not os.path.exists(os.path.join(REF, "gpssim.c")):
         sys.exit("no reference sources at " + REF)
-    build(WORK, OUT, False)
-    build(WORK + "_intcarr", OUT_INT, True)
+    # a scratch directory of this run's own (a fixed name may be left over from another user)
+    work = tempfile.mkdtemp(prefix="gss_integ_")
+    try:
+        build(os.path.join(work, "float"), OUT, False)
+        build(os.path.join(work, "intcarr"), OUT_INT, True)
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
 
 
 if __name__ == "__main__":

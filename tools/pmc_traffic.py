@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """profiles/pmc_traffic.json from a bench.py live-profile directory (GSS_PROF_SAVE=<dir> python
-bench.py ..., whose JSON line is in <dir>/bench.log): HBM bytes per launch of the fast kernel from
+bench.py --full ..., whose JSON line is in <dir>/bench.log): HBM bytes per launch of the fast kernel from
 the PMC passes (WRITE_SIZE exact, FETCH_SIZE x2 for gfx950 wide reads; both KiB,
 MI355X_MICROARCH.md §HBM), keyed by the bench workload string and library build, with the
 profiled kernel time next to the un-profiled run's own event time (bench.py attaches the record

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 TAG=${1:-w}
 OUT=gpurun_out/profw_$TAG
 mkdir -p $OUT
-BA="--steps ${STEPS:-10} --warmup ${WARMUP:-3} --no-exact --no-configs --no-e2e --no-cpu-baseline --no-pmc --no-sustained"
+BA="--full --steps ${STEPS:-10} --warmup ${WARMUP:-3} --no-exact --no-configs --no-e2e --no-cpu-baseline --no-pmc --no-sustained"
 run() {  # name, rocprofv3 args...
     local name=$1; shift
     timeout -k 10 400 rocprofv3 "$@" -d $OUT/$name -o $name -f csv -- python3 bench.py $BA \

@@ -15,7 +15,10 @@ set -o pipefail
 cd "$(dirname "$0")/.."
 OUT=${OUT:-profiles/round5/sanitize}
 SECS=${SECS:-300}
-mkdir -p $OUT /tmp/gss_san
+mkdir -p $OUT
+# the builds go to a scratch directory of this run's own (a fixed name may belong to another user)
+WORK=$(mktemp -d) || exit 1
+trap 'rm -rf "$WORK"' EXIT
 SRC="gps-sdr-sim_amd/csrc/host/*.c gps-sdr-sim_amd/csrc/cli/cli_args.c tests/helpers/run_harness.c"
 CF="-O1 -g -fno-omit-frame-pointer -ffp-contract=off -fno-fast-math -D_FILE_OFFSET_BITS=64 -Iinclude"
 NAV=tests/golden/data/brdc3540.14n
@@ -41,7 +44,7 @@ build() {  # san dir
 for san in thread address,undefined; do
     tag=${san%%,*}
     # gss_run on the fake device: C host sources by gcc, the C++ ones by g++
-    d=/tmp/gss_san/fake_$tag
+    d=$WORK/fake_$tag
     rm -rf $d
     mkdir -p $d
     build $san $d || exit 1
@@ -63,7 +66,7 @@ for san in thread address,undefined; do
         tail -3 $log
         [ $r -eq 0 ] || rc=1
     done
-    exe=/tmp/gss_san/run_harness_$tag
+    exe=$WORK/run_harness_$tag
     gcc -fsanitize=$san -o $exe $host_objs $d/run_harness.o -lm -lpthread || exit 1
     for args in "$SECS 512 1" "${HARNESS_ARGS:-60 64 16}"; do
         log=$OUT/${tag}_$(echo $args | tr ' ' _).log
