@@ -2,6 +2,7 @@
  * cli_args.c — option surface of the reference (getopt string "e:u:g:c:l:o:s:b:T:t:d:iv",
  * gpssim.c:1756-1852), same validation messages and the same last-option-wins behaviour.
  */
+#include <errno.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,6 +43,90 @@ static void set_start(gss_cli_t *c, int y, int m, int d, int hh, int mm, double 
     c->opt.start_sec = sec;
 }
 
+/* a finite number with nothing after it */
+static int parse_real(const char *s, double *v)
+{
+    char *end = NULL;
+    if (!s || !*s)
+        return 1;
+    *v = strtod(s, &end);
+    return *end != '\0' || !isfinite(*v);
+}
+
+/* The noise options into c->impair.
+     --cn0=<dB-Hz>        sigma = 250 sqrt(fs / (2 10^(cn0/10))) LSB per component: 250 is the carrier
+                          table's amplitude, so this is the C/N0 of a satellite at gain 128 (path
+                          loss 1 at antenna boresight); fs as the run uses it, a multiple of 10 Hz
+                          (gpssim.c:1877-1881)
+     --noise-sigma=<LSB>  sigma directly
+     --noise-shift=<s>    0..8, or auto (default): the least s with (4 sigma + 2047) / 2^s <= R, R =
+                          32767 for -b 16 and 2047 for -b 8 (what >> 4 takes to the 8-bit range);
+                          0 for -b 1, which keeps only the sign
+     --seed=<u64>         default 0 */
+static int noise_options(gss_cli_t *c, const char *o_cn0, const char *o_sigma, const char *o_shift,
+                         const char *o_seed)
+{
+    if (o_cn0 && o_sigma) {
+        fprintf(stderr, "ERROR: --cn0 and --noise-sigma are mutually exclusive.\n");
+        return 1;
+    }
+    if (!o_cn0 && !o_sigma) {
+        if (o_shift || o_seed) {
+            fprintf(stderr, "ERROR: --noise-shift and --seed need --cn0 or --noise-sigma.\n");
+            return 1;
+        }
+        return 0;
+    }
+    double v = 0.0, q8;
+    if (o_cn0) {
+        if (parse_real(o_cn0, &v) || v < -100.0 || v > 200.0) {
+            fprintf(stderr, "ERROR: Invalid C/N0.\n");
+            return 1;
+        }
+        const double fs = floor(c->opt.samp_freq / 10.0) * 10.0;
+        q8 = floor(256.0 * 250.0 * sqrt(fs / (2.0 * pow(10.0, v / 10.0))) + 0.5);
+    } else {
+        if (parse_real(o_sigma, &v) || v < 0.0) {
+            fprintf(stderr, "ERROR: Invalid noise sigma.\n");
+            return 1;
+        }
+        q8 = floor(256.0 * v + 0.5);
+    }
+    if (!(q8 <= (double)0x00FFFFFF)) {
+        fprintf(stderr, "ERROR: Noise sigma out of range (at most 65535 LSB).\n");
+        return 1;
+    }
+    c->impair.sigma_q8 = (uint32_t)q8;
+    if (o_shift && strcmp(o_shift, "auto") != 0) {
+        if (parse_real(o_shift, &v) || v < 0.0 || v > 8.0 || v != floor(v)) {
+            fprintf(stderr, "ERROR: Invalid noise shift (0..8 or auto).\n");
+            return 1;
+        }
+        c->impair.shift = (int32_t)v;
+    } else {
+        const double peak = 4.0 * (q8 / 256.0) + 2047.0;
+        const double room = c->opt.data_format == GSS_FMT_SC16 ? 32767.0 : 2047.0;
+        int s = 0;
+        while (c->opt.data_format != GSS_FMT_SC01 && s < 8 && peak > room * (double)(1 << s))
+            s++;
+        c->impair.shift = s;
+    }
+    c->impair.seed = 0;
+    if (o_seed) {
+        char *end = NULL;
+        errno = 0;
+        const unsigned long long u = strtoull(o_seed, &end, 0);
+        if (!*o_seed || *o_seed == '-' || *o_seed == '+' || *o_seed == ' ' || *end != '\0' ||
+            errno) {
+            fprintf(stderr, "ERROR: Invalid seed.\n");
+            return 1;
+        }
+        c->impair.seed = (uint64_t)u;
+    }
+    c->has_impair = 1;
+    return 0;
+}
+
 int gss_cli_parse(int argc, char **argv, gss_cli_t *c)
 {
     memset(c, 0, sizeof *c);
@@ -58,7 +143,26 @@ int gss_cli_parse(int argc, char **argv, gss_cli_t *c)
        taken out before the reference's getopt loop sees the arguments */
     char *av[argc + 1];
     int ac = 0;
+    /* additive noise (extensions, taken out the same way): --cn0=<dB-Hz> or --noise-sigma=<LSB>,
+       --noise-shift=<0..8|auto>, --seed=<u64>; resolved once -s and -b are known */
+    const char *o_cn0 = NULL, *o_sigma = NULL, *o_shift = NULL, *o_seed = NULL;
     for (int i = 0; i < argc; i++) {
+        if (i > 0 && strncmp(argv[i], "--cn0=", 6) == 0) {
+            o_cn0 = argv[i] + 6;
+            continue;
+        }
+        if (i > 0 && strncmp(argv[i], "--noise-sigma=", 14) == 0) {
+            o_sigma = argv[i] + 14;
+            continue;
+        }
+        if (i > 0 && strncmp(argv[i], "--noise-shift=", 14) == 0) {
+            o_shift = argv[i] + 14;
+            continue;
+        }
+        if (i > 0 && strncmp(argv[i], "--seed=", 7) == 0) {
+            o_seed = argv[i] + 7;
+            continue;
+        }
         if (i > 0 && strncmp(argv[i], "--carrier=", 10) == 0) {
             if (strcmp(argv[i] + 10, "int") == 0)
                 c->opt.carrier_int = 1;
@@ -172,5 +276,5 @@ int gss_cli_parse(int argc, char **argv, gss_cli_t *c)
         fprintf(stderr, "ERROR: Invalid duration.\n");
         return 1;
     }
-    return 0;
+    return noise_options(c, o_cn0, o_sigma, o_shift, o_seed);
 }

@@ -327,7 +327,11 @@ static int run_rank(const gss_cli_t *cli, gss_scn *scn, const gss_scn_info_t *in
     /* GSS_HANDOFF_SPEC=0: the carriers first, then the chain (no speculation; every rank of a
        run must agree) */
     const int spec = env_int("GSS_HANDOFF_SPEC", 1);
-    gss_run_opts_t ro = {handoff_in, handoff_out, &h, spec ? handoff_predict : NULL};
+    const int handoff = run_id && *run_id;
+    /* the noise does not change the carriers, so the hand-off stays as it is */
+    gss_run_opts_t ro = {handoff ? handoff_in : NULL, handoff ? handoff_out : NULL, &h,
+                         handoff && spec ? handoff_predict : NULL,
+                         cli->has_impair ? &cli->impair : NULL};
     if (run_id && *run_id) {
         if (rank > 0)
             snprintf(h.in_path, sizeof h.in_path, "%s.gss-carr-%s-%lld", cli->out_file, run_id,
@@ -344,7 +348,7 @@ static int run_rank(const gss_cli_t *cli, gss_scn *scn, const gss_scn_info_t *in
     }
     if (gss_run_ex(dev, scn, first, last - first, env_int("GSS_BATCH", 128),
                    env_int("GSS_THREADS", default_threads()), pwrite_sink, &c,
-                   run_id && *run_id ? &ro : NULL)) {
+                   handoff || cli->has_impair ? &ro : NULL)) {
         fprintf(stderr, "\nERROR: rank %d: %s\n", rank, gss_last_error());
         return 1;
     }
@@ -377,6 +381,9 @@ int main(int argc, char **argv)
         fprintf(stderr, "ERROR: invalid RANK %d / WORLD_SIZE %d.\n", rank, world);
         return 1;
     }
+    if (cli.has_impair && rank == 0)
+        fprintf(stderr, "Noise: sigma_q8 = %u, shift = %d, seed = %llu\n", cli.impair.sigma_q8,
+                cli.impair.shift, (unsigned long long)cli.impair.seed);
     if (world > 1)
         return run_rank(&cli, scn, &info, rank, world);
 
@@ -400,7 +407,11 @@ int main(int argc, char **argv)
     clock_t t0 = clock();
     /* planning, upload, both kernel stages, download and fwrite overlap inside gss_run; the
        sink sees each batch's bytes in run order (gpssim.c:2276/2283/2287) */
-    if (gss_run(dev, scn, 0, -1, batch, threads, write_sink, fp)) {
+    gss_run_opts_t ro;
+    memset(&ro, 0, sizeof ro);
+    ro.impair = &cli.impair;
+    if (gss_run_ex(dev, scn, 0, -1, batch, threads, write_sink, fp,
+                   cli.has_impair ? &ro : NULL)) {
         fprintf(stderr, "\nERROR: %s\n", gss_last_error());
         return 1;
     }

@@ -50,6 +50,13 @@ extern "C" void gss_pool_select(int id);             /* pool.c */
 /* n bytes from src to dst by a copy kernel on st: pinned host or device memory on either side
    (gss_producers.hip; not exported) */
 int run_copy_launch(void *dst, const void *src, size_t n, hipStream_t st);
+/* The impairment's launch (gss_impair.hip) through a weak reference: a build of this file without
+   the kernels (the CPU harness, tests/helpers) links, and refuses runs that ask for noise unless
+   it supplies a launch of its own. */
+extern "C" __attribute__((weak)) int gss_impair_device(gss_dev *d, const gss_impair_t *p,
+                                                       const int16_t *iq, uint64_t sample0,
+                                                       size_t n, int fmt, void *out,
+                                                       void *stream);
 
 #define RUN_TRY(x)                                                                           \
     do {                                                                                     \
@@ -331,6 +338,9 @@ struct Slot {
     size_t d_in_cap = 0;
     uint8_t *d_out = nullptr, *h_out = nullptr;
     size_t h_out_bytes = 0, d_out_bytes = 0;   /* their sizes (pool_get / pool_put)        */
+    uint8_t *d_imp = nullptr;        /* additive noise into SC08 / SC01: the impaired bytes (d_out
+                                        holds the SC16 render; SC16 is impaired in place)   */
+    size_t d_imp_bytes = 0;
     int32_t *d_status = nullptr, *h_status = nullptr;
     hipEvent_t rendered = nullptr;   /* compute stream: the slot's kernels are done      */
     hipEvent_t done = nullptr;       /* copy stream: the slot's bytes are in h_out        */
@@ -364,6 +374,9 @@ struct Run {
     int64_t start = 0;               /* the handle's next block when the run began (an earlier
                                         run, a seek): the planner's and rows thread's cursor   */
     const gss_run_opts_t *opts;      /* carrier hand-off (gss_run_ex), or null */
+    const gss_impair_t *impair = nullptr;   /* additive noise (opts->impair), or null: the blocks
+                                               render at SC16 and the impairment writes fmt_out */
+    int fmt_out = 0;                 /* the scenario's format: what the sink receives          */
     /* with opts->carr_in: the whole range planned up front (rows, carriers, checkpoints) */
     std::vector<gss_chan_blk_t> pre_blk;
     std::vector<int32_t> pre_nch;
@@ -1339,6 +1352,22 @@ SlotDev slot_dev(const Slot &sl)
     return v;
 }
 
+/* Additive noise: blocks [b0, b0 + nblk) of the slot, rendered at SC16 into d_out, through the
+   impairment into the run's format on st (one launch: the blocks' samples are consecutive in the
+   run, sample0 = run block * n_per_blk) */
+int impair_blocks(Run &r, Slot &sl, int b0, int nblk, hipStream_t st)
+{
+    const size_t n = (size_t)r.n_per_blk;
+    uint8_t *in = sl.d_out + 4 * n * (size_t)b0;
+    uint8_t *out = sl.d_imp ? sl.d_imp + gss_block_bytes(r.n_per_blk, r.fmt_out) * (size_t)b0 : in;
+    return gss_impair_device(r.dev, r.impair, (const int16_t *)in,
+                             (uint64_t)(sl.first + b0) * (uint64_t)n, n * (size_t)nblk, r.fmt_out,
+                             out, st);
+}
+
+/* the slot's bytes on the device, as the sink receives them */
+uint8_t *slot_bytes(const Slot &sl) { return sl.d_imp ? sl.d_imp : sl.d_out; }
+
 /* GPU proofs, run ahead (planner thread, right after the slot is planned): the slot's rows go
    to its device buffer on its own stream, its new nav rows are built on the planner's nav
    stream (in slot order: a row may continue the one before it), and the proof kernel runs as
@@ -1438,13 +1467,16 @@ int submit_proven(gss_dev *d, Run &r, Slot &sl, int n_per_blk, int fmt, size_t b
     int rc = gss_synth_lin_device(d, v.blk, v.nch, sl.nch_max, v.lin, v.fast, v.fast + sl.nb, nf,
                                   v.ck, r.d_ca, 32, r.d_nav, n_rows > 0 ? n_rows : 1, sl.nb,
                                   n_per_blk, fmt, sl.d_out, sl.d_status, st);
+    if (!rc && r.impair)
+        rc = impair_blocks(r, sl, 0, sl.nb, st);
     if (rc)
         return rc;
     RUN_TRY(hipEventRecord(sl.rendered, st));
     RUN_TRY(hipStreamWaitEvent(cp, sl.rendered, 0));
     if (sl.tc)
         RUN_TRY(hipEventRecord(sl.tc, cp));
-    RUN_TRY(hipMemcpyAsync(sl.h_out, sl.d_out, bb * (size_t)sl.nb, hipMemcpyDeviceToHost, cp));
+    RUN_TRY(hipMemcpyAsync(sl.h_out, slot_bytes(sl), bb * (size_t)sl.nb, hipMemcpyDeviceToHost,
+                           cp));
     RUN_TRY(hipMemcpyAsync(sl.h_status, sl.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, cp));
     RUN_TRY(hipMemcpyAsync(sl.fast, v.fast, sizeof(int32_t) * (size_t)sl.nb,
                            hipMemcpyDeviceToHost, cp));
@@ -1512,6 +1544,8 @@ int submit(gss_dev *d, Run &r, Slot &sl, const uint32_t *d_ca, int n_per_blk, in
         rc = gss_synth_device(d, d_blk, d_nch, sl.nch_max, d_ck, d_ca, 32, d_nav, n_rows,
                               sl.nb, n_per_blk, fmt, sl.d_out, nullptr, sl.d_status, st);
     }
+    if (!rc && r.impair)
+        rc = impair_blocks(r, sl, 0, sl.nb, st);
     if (rc)
         return rc;
     const double tq2 = trace_on() ? tnow() : 0.0;
@@ -1519,7 +1553,8 @@ int submit(gss_dev *d, Run &r, Slot &sl, const uint32_t *d_ca, int n_per_blk, in
     RUN_TRY(hipStreamWaitEvent(cp, sl.rendered, 0));
     if (sl.tc)
         RUN_TRY(hipEventRecord(sl.tc, cp));
-    RUN_TRY(hipMemcpyAsync(sl.h_out, sl.d_out, bb * (size_t)sl.nb, hipMemcpyDeviceToHost, cp));
+    RUN_TRY(hipMemcpyAsync(sl.h_out, slot_bytes(sl), bb * (size_t)sl.nb, hipMemcpyDeviceToHost,
+                           cp));
     RUN_TRY(hipMemcpyAsync(sl.h_status, sl.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, cp));
     RUN_TRY(hipEventRecord(sl.done, cp));
     if (trace_on())
@@ -1566,7 +1601,9 @@ int redo_rejected(gss_dev *d, Run &r, Slot &sl, const uint32_t *d_ca, int n_rows
         int j = i + 1;
         while (j < nf && sl.fast[sl.nb + j] == b0 + (j - i))
             j++;
-        RUN_TRY(hipMemcpyAsync(sl.h_out + bb * (size_t)b0, sl.d_out + bb * (size_t)b0,
+        if (r.impair && (rc = impair_blocks(r, sl, b0, j - i, st)) != 0)
+            return rc;
+        RUN_TRY(hipMemcpyAsync(sl.h_out + bb * (size_t)b0, slot_bytes(sl) + bb * (size_t)b0,
                                bb * (size_t)(j - i), hipMemcpyDeviceToHost, st));
         i = j;
     }
@@ -1704,9 +1741,22 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
     if (bb == 0)
         return gss_fail(GSS_E_ARG, "invalid format %d for %d samples/block", info.data_format,
                         info.n_per_blk);
+    /* additive noise: the blocks render at SC16 (fmt, bb_r) and the impairment writes the
+       scenario's format (bb bytes per block: what the sink receives) */
+    const gss_impair_t *imp = opts ? opts->impair : nullptr;
+    if (imp && (imp->sigma_q8 > 0x00FFFFFFu || imp->shift < 0 || imp->shift > 8))
+        return gss_fail(GSS_E_ARG, "invalid impairment (sigma_q8 <= 0xFFFFFF, shift 0..8)");
+    if (imp && !gss_impair_device)
+        return gss_fail(GSS_E_STATE, "additive noise requested, but this build has no "
+                                     "impairment launch (gss_impair_device)");
+    const int fmt = imp ? GSS_FMT_SC16 : info.data_format;
+    const size_t bb_r = imp ? (size_t)info.n_per_blk * 4 : bb;
     Run r;
     r.scn = s;
     r.opts = opts;
+    r.impair = imp;
+    r.fmt_out = info.data_format;
+    r.dev = d;
     r.carrier_int = info.carrier_int;
     r.threads = threads > 0 ? threads : 1;
     r.n_per_blk = info.n_per_blk;
@@ -1721,8 +1771,8 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
         r.upload_dev = !(up && strcmp(up, "dma") == 0);
     }
     r.batch = batch > 0 ? batch : 100;
-    if ((size_t)r.batch * bb > SLOT_OUT_MAX)
-        r.batch = (int)(SLOT_OUT_MAX / bb) > 0 ? (int)(SLOT_OUT_MAX / bb) : 1;
+    if ((size_t)r.batch * bb_r > SLOT_OUT_MAX)
+        r.batch = (int)(SLOT_OUT_MAX / bb_r) > 0 ? (int)(SLOT_OUT_MAX / bb_r) : 1;
     r.first = first_block;
     r.last = n_blocks < 0 ? INT64_MAX : first_block + n_blocks;
     /* the handle may have produced blocks already (an earlier run or seek): the run continues
@@ -1749,6 +1799,7 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
             pin_free(sl.nav); pin_free(sl.h_status);
             pool_put(sl.h_out, sl.h_out_bytes, true, ordinal);
             pool_put(sl.d_out, sl.d_out_bytes, false, ordinal);
+            pool_put(sl.d_imp, sl.d_imp_bytes, false, ordinal);
             pin_free(sl.lin); pin_free(sl.fast); pin_free(sl.anch);
             dev_free(sl.d_in); dev_free(sl.d_status);
             if (sl.done) (void)hipEventDestroy(sl.done);
@@ -1808,8 +1859,11 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
                     hipSuccess ||
                 pin_alloc((void **)&sl.h_status, sizeof(int32_t)) !=
                     hipSuccess ||
-                pool_get((void **)&sl.d_out, bb * nb, false, ordinal, &sl.d_out_bytes) !=
+                pool_get((void **)&sl.d_out, bb_r * nb, false, ordinal, &sl.d_out_bytes) !=
                     hipSuccess ||
+                (imp && fmt != r.fmt_out &&
+                 pool_get((void **)&sl.d_imp, bb * nb, false, ordinal, &sl.d_imp_bytes) !=
+                     hipSuccess) ||
                 dev_alloc((void **)&sl.d_status, sizeof(int32_t)) != hipSuccess ||
                 hipEventCreateWithFlags(&sl.done, trace_on() ? hipEventDefault
                                                              : hipEventDisableTiming) != hipSuccess ||
@@ -1985,7 +2039,7 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
                                           r.spec_st);
         }
     }
-    err = run_main(d, r, info.n_per_blk, info.data_format, bb, sink, user, st, cp, d_ca);
+    err = run_main(d, r, info.n_per_blk, fmt, bb, sink, user, st, cp, d_ca);
     {
         std::lock_guard<std::mutex> lk(r.mu);
         r.abort = 1;

@@ -97,9 +97,26 @@ class _Opts(C.Structure):
     ]
 
 
+class Impair(C.Structure):
+    """gss_impair_t: seeded additive Gaussian noise, sigma_q8 / 256 LSB of the 16-bit sample per
+    component, after which every sample is shifted right by `shift` (0..8) with rounding."""
+    _fields_ = [("seed", C.c_uint64), ("sigma_q8", C.c_uint32), ("shift", C.c_int32)]
+
+    def __init__(self, sigma_q8=0, shift=0, seed=0):
+        super().__init__(int(seed), int(sigma_q8), int(shift))
+
+    def __repr__(self):
+        return f"Impair(sigma_q8={self.sigma_q8}, shift={self.shift}, seed={self.seed})"
+
+
 class _Cli(C.Structure):
     _fields_ = [("opt", _Opts), ("nav_file", C.c_char * 256), ("motion_file", C.c_char * 256),
-                ("out_file", C.c_char * 256)]
+                ("out_file", C.c_char * 256), ("impair", Impair), ("has_impair", C.c_int)]
+
+
+class _RunOpts(C.Structure):                         # gss_run_opts_t
+    _fields_ = [("carr_in", C.c_void_p), ("carr_out", C.c_void_p), ("carr_user", C.c_void_p),
+                ("carr_predict", C.c_void_p), ("impair", C.POINTER(Impair))]
 
 
 class _Info(C.Structure):
@@ -141,6 +158,10 @@ _SIGS = {
                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gss_first_below": (C.c_uint64, [C.c_uint64] * 5),
     "gss_hits_mod": (C.c_int, [C.c_uint64] * 5 + [_P, C.c_int, C.c_int]),
+    "gss_noise_table": (C.c_int, [_P]),
+    "gss_impair_host": (C.c_int, [C.POINTER(Impair), _P, C.c_uint64, C.c_size_t, C.c_int, _P]),
+    "gss_impair_device": (C.c_int, [_P, C.POINTER(Impair), _P, C.c_uint64, C.c_size_t, C.c_int,
+                                    _P, _P]),
     "gss_dev_timing": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float),
                                  C.POINTER(C.c_float)]),
     "gss_dev_timing_lin": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
@@ -259,6 +280,28 @@ def nav_rows_host(src, first=0, rows=None):
     if first:
         out[:first] = rows[:first]
     _check(lib().gss_nav_rows_host(_ptr(src), first, len(src), _ptr(out)))
+    return out
+
+
+def noise_table():
+    """the half-normal inverse-CDF table of the additive noise (gss_noise_table): int32[4097]"""
+    out = np.zeros(4097, np.int32)
+    _check(lib().gss_noise_table(_ptr(out)))
+    return out
+
+
+def impair_bytes(n, fmt):
+    """bytes n impaired samples take in format fmt"""
+    return {FMT_SC16: 4 * n, FMT_SC08: 2 * n, FMT_SC01: n // 4}[fmt]
+
+
+def impair_host(imp, iq, sample0, fmt):
+    """The impairment on the host (gss_impair_host): iq int16[2 n], the noise-free components of
+    samples [sample0, sample0 + n); returns the bytes of format fmt as uint8."""
+    iq = np.ascontiguousarray(iq, np.int16).reshape(-1)
+    n = len(iq) // 2
+    out = np.zeros(impair_bytes(n, fmt) if fmt in (1, 8, 16) else 0, np.uint8)
+    _check(lib().gss_impair_host(C.byref(imp), _ptr(iq), int(sample0), n, int(fmt), _ptr(out)))
     return out
 
 
@@ -384,7 +427,11 @@ class Scenario:
         self._h = C.c_void_p()
         _check(lib().gss_scn_open(C.byref(self._h), C.byref(cli.opt)))
         self._init_info()
+        if cli.has_impair:                             # --cn0 / --noise-sigma (Device.run(impair=))
+            self.impair = Impair(cli.impair.sigma_q8, cli.impair.shift, cli.impair.seed)
         return self, cli.out_file.decode()
+
+    impair = None                # the command line's noise options (from_cli), else None
 
     def _init_info(self):
         inf = _Info()
@@ -722,10 +769,18 @@ class Device:
                                        nav_ptr, n_nav, nblk, n_per_blk, fmt, out_ptr,
                                        status_ptr or None, stream or None))
 
-    def run(self, scn, sink, first_block=0, n_blocks=-1, batch=100, threads=8):
+    def impair_device(self, imp, iq_ptr, sample0, n, fmt, out_ptr, stream=0):
+        """gss_impair_device: the additive noise over n SC16 samples at device pointer iq_ptr
+        (absolute index sample0 on), format fmt to out_ptr (== iq_ptr: SC16 only); async."""
+        _check(lib().gss_impair_device(self._h, C.byref(imp), C.c_void_p(iq_ptr), int(sample0),
+                                       int(n), int(fmt), C.c_void_p(out_ptr),
+                                       C.c_void_p(stream or None)))
+
+    def run(self, scn, sink, first_block=0, n_blocks=-1, batch=100, threads=8, impair=None):
         """Stream blocks [first_block, first_block + n_blocks) of Scenario scn through gss_run;
         sink(memoryview, first_block, nblocks) gets each batch's bytes in run order (the view
-        is valid only during the call).  An exception in sink stops the run and is re-raised."""
+        is valid only during the call).  An exception in sink stops the run and is re-raised.
+        impair: an Impair (additive noise, gss_run_opts_t.impair), None: off."""
         err = []
 
         def _sink(user, ptr, n, first, nb):
@@ -737,7 +792,12 @@ class Device:
                 return 1
 
         cb = SINK_FN(_sink)
-        rc = lib().gss_run(self._h, scn._h, first_block, n_blocks, batch, threads, cb, None)
+        if impair is None:
+            rc = lib().gss_run(self._h, scn._h, first_block, n_blocks, batch, threads, cb, None)
+        else:
+            ro = _RunOpts(None, None, None, None, C.pointer(impair))
+            rc = lib().gss_run_ex(self._h, scn._h, first_block, n_blocks, batch, threads, cb,
+                                  None, C.byref(ro))
         if err:
             raise err[0]
         _check(rc)

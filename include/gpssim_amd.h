@@ -192,6 +192,39 @@ int gss_synth_host(gss_dev *d, const gss_chan_blk_t *blk, const int32_t *nch,
                    const double *carr_ck, const uint32_t *ca_bits, int n_ca, const uint32_t *nav, int n_nav,
                    int nblk, int n_per_blk, int fmt, void *out, double *carr_end);
 
+/* ---- additive noise ---------------------------------------------------------------------------
+   White Gaussian noise added to the 16-bit samples before the format's quantiser (an extension:
+   the reference emits the noise-free sum of satellites).  Exact integer arithmetic, a function
+   of the seed and the sample's absolute index in the run (run block * n_per_blk + position), so
+   the bytes do not depend on how a run is cut into batches, windows or ranks.  For sample n
+   with noise-free components x16 (as gpssim.c:2262-2263 stores them):
+     words   w[0..3] = Philox4x32-10(counter {lo32(n >> 1), hi32(n >> 1), 0, 0}, key {lo32(seed),
+             hi32(seed)}); I takes w[2 (n & 1)], Q takes w[2 (n & 1) + 1]
+     normal  from a word u: sign = u >> 31, idx = (u >> 19) & 4095, f = (u >> 3) & 0xFFFF,
+             mag = T[idx] + (((T[idx + 1] - T[idx]) * f) >> 16), T = gss_noise_table
+     noise   g = (mag * sigma_q8 + 2^23) >> 24, negated if sign
+     output  w = (x16 + g + ((1 << shift) >> 1)) >> shift (arithmetic); SC16 clamp(w, -32768,
+             32767); SC08 clamp(w >> 4, -128, 127); SC01 bit = w > 0, packed as gpssim.c:2266-2276 */
+typedef struct gss_impair {
+    uint64_t seed;
+    uint32_t sigma_q8;           /* noise sigma per component in 1/256 LSB of the 16-bit sample,
+                                    <= 0x00FFFFFF                                              */
+    int32_t  shift;              /* 0..8: common attenuation that makes room for the noise     */
+} gss_impair_t;
+
+/* T[4097], Q16: T[i] = round(65536 * Phi^-1(0.5 + i / 8192)) for i < 4096 and T[4096] =
+   round(65536 * Phi^-1(1 - 1/32768)) = 262719 (4.009 sigma).                                  */
+int gss_noise_table(int32_t *out);
+/* The impairment of samples [sample0, sample0 + n) on the host: iq holds their 2 n noise-free
+   int16 components, out receives n * 4 (SC16), n * 2 (SC08) or n / 4 (SC01; n % 4 == 0) bytes.
+   out == iq is allowed for SC16 only.                                                         */
+int gss_impair_host(const gss_impair_t *p, const int16_t *iq, uint64_t sample0, size_t n,
+                    int fmt, void *out);
+/* The same on the device: device pointers, asynchronous on stream (the first call on a device
+   uploads the table synchronously).                                                           */
+int gss_impair_device(gss_dev *d, const gss_impair_t *p, const int16_t *iq, uint64_t sample0,
+                      size_t n, int fmt, void *out, void *stream);
+
 /* Kernel timing from HIP events recorded on the launch stream around every Stage A and Stage B
    launch (gss_synth_device, gss_anchor_device, gss_render_device; rings of the last 256 of
    each).  reset!=0 clears the rings (no sync); otherwise waits for the last launches and
@@ -240,6 +273,9 @@ typedef struct gss_opts {
 typedef struct gss_cli {
     gss_opts_t opt;
     char nav_file[256], motion_file[256], out_file[256];
+    /* extensions: --cn0=<dB-Hz> | --noise-sigma=<LSB>, --noise-shift=<0..8|auto>, --seed=<u64> */
+    gss_impair_t impair;
+    int has_impair;
 } gss_cli_t;
 int gss_cli_parse(int argc, char **argv, gss_cli_t *cli);
 void gss_cli_usage(void);
@@ -524,6 +560,9 @@ typedef struct gss_run_opts {
        no fast path) calls it once with round -1 and map == start_out == NULL, so that the
        ranks after it can fail at once instead of waiting for maps that never come.          */
     int (*carr_predict)(void *user, int round, const double *map, double *start_out);
+    /* Optional (NULL: off): additive noise.  Every block renders at SC16 and the impairment
+       (gss_impair_device, sample0 = run block * n_per_blk) writes the scenario's format.       */
+    const gss_impair_t *impair;
 } gss_run_opts_t;
 int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int batch,
                int threads, gss_sink_fn sink, void *user, const gss_run_opts_t *opts);

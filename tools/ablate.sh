@@ -16,6 +16,7 @@ $HIPCC $F -c ${SYNTH_SRC:-gps-sdr-sim_amd/csrc/hip/gss_synth.hip} -o _var/$name/
 $HIPCC $F -c gps-sdr-sim_amd/csrc/hip/gss_run.hip -o _var/$name/obj/gss_run.o
 $HIPCC $F -c gps-sdr-sim_amd/csrc/hip/gss_producers.hip -o _var/$name/obj/gss_producers.o
 $HIPCC $F -c gps-sdr-sim_amd/csrc/hip/gss_proof.hip -o _var/$name/obj/gss_proof.o
+$HIPCC $F -c gps-sdr-sim_amd/csrc/hip/gss_impair.hip -o _var/$name/obj/gss_impair.o
 HOSTOBJ=gps-sdr-sim_amd/obj/host/*.o
 if [ -n "$HOSTFLAGS" ]; then          # the host proof must agree with the kernel (e.g. GSS_LIN_CH)
     mkdir -p _var/$name/obj/host
@@ -28,4 +29,4 @@ fi
 $HIPCC -shared -fPIC --offload-arch=gfx950 -Wl,--version-script=gps-sdr-sim_amd/exports.map \
     -o _var/$name/libgpssim_amd.so $HOSTOBJ \
     _var/$name/obj/gss_synth.o _var/$name/obj/gss_run.o _var/$name/obj/gss_producers.o \
-    _var/$name/obj/gss_proof.o -lm -lpthread
+    _var/$name/obj/gss_proof.o _var/$name/obj/gss_impair.o -lm -lpthread
