@@ -23,6 +23,7 @@ if os.environ.get("GSS_LIB_PATH") and os.environ.get("GSS_ALLOW_LIB_OVERRIDE") !
 LIB_PATH = os.environ.get("GSS_LIB_PATH") or _INTREE
 IN_TREE = os.path.abspath(LIB_PATH) == os.path.abspath(_INTREE)
 CLI_PATH = os.path.join(PKG_DIR, "bin", "gps-sdr-sim")
+ACQ_CLI_PATH = os.path.join(PKG_DIR, "bin", "gps-sdr-acq")
 
 MAXCH = 16
 CA_WORDS = 32
@@ -77,6 +78,10 @@ NAV_SRC_DTYPE = np.dtype([("sbf", "<u4", (5, 10)), ("tow", "<u4"), ("wn", "<u4")
                           ("next", "<i4"), ("head", "<u4", (10,))])
 assert NAV_SRC_DTYPE.itemsize == 256
 NAV_HEAD_INIT, NAV_HEAD_GIVEN = -1, -2
+# gss_acq_peak_t: one PRN's peak and floor of the acquisition search (gss_acquire_*)
+ACQ_PEAK_DTYPE = np.dtype([("peak", "<u8"), ("floor_sum", "<u8"), ("floor_cnt", "<u4"),
+                           ("tau", "<i4"), ("bin", "<i4"), ("prn", "<i4")])
+assert ACQ_PEAK_DTYPE.itemsize == 32
 
 
 class GssError(RuntimeError):
@@ -107,6 +112,47 @@ class Impair(C.Structure):
 
     def __repr__(self):
         return f"Impair(sigma_q8={self.sigma_q8}, shift={self.shift}, seed={self.seed})"
+
+
+class Acq(C.Structure):
+    """gss_acq_t: an acquisition search.  fs_hz, fmt (16 / 8 / 1), coh_ms x n_coh windows, bins
+    -n_half..n_half of bin_hz (default 500 / coh_ms), qshift (-1: auto), prns (iterable of 1..32,
+    default all)."""
+    _fields_ = [("fs_hz", C.c_int32), ("fmt", C.c_int32), ("coh_ms", C.c_int32),
+                ("n_coh", C.c_int32), ("bin_hz", C.c_int32), ("n_half", C.c_int32),
+                ("qshift", C.c_int32), ("prn_mask", C.c_uint32)]
+
+    def __init__(self, fs_hz, fmt=16, coh_ms=1, n_coh=10, bin_hz=None, n_half=20, qshift=-1,
+                 prns=None):
+        mask = 0xFFFFFFFF
+        if prns is not None:
+            mask = 0
+            for p in prns:
+                if not 1 <= int(p) <= 32:
+                    raise ValueError(f"PRN {p} outside 1..32")
+                mask |= 1 << (int(p) - 1)
+        super().__init__(int(fs_hz), int(fmt), int(coh_ms), int(n_coh),
+                         int(500 // max(int(coh_ms), 1) if bin_hz is None else bin_hz),
+                         int(n_half), int(qshift), mask)
+
+    def sizes(self):
+        """(L, T, N, E, n_prn): samples per window, code phases, samples read, excluded
+        half-width, selected PRNs (gss_acq_sizes)"""
+        L, T, E, P = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        N = C.c_int64()
+        _check(lib().gss_acq_sizes(C.byref(self), C.byref(L), C.byref(T), C.byref(N),
+                                   C.byref(E), C.byref(P)))
+        return L.value, T.value, N.value, E.value, P.value
+
+    def sample_bytes(self):
+        """bytes the search reads from its sample pointer"""
+        n = self.sizes()[2]
+        return {FMT_SC16: 4 * n, FMT_SC08: 2 * n, FMT_SC01: (n + 3) // 4}[self.fmt]
+
+
+class _Truth(C.Structure):                           # gss_acq_truth_t
+    _fields_ = [("tau", C.c_double), ("doppler_hz", C.c_double), ("cn0_offset_db", C.c_double),
+                ("prn", C.c_int32), ("pad", C.c_int32)]
 
 
 class _Cli(C.Structure):
@@ -162,6 +208,14 @@ _SIGS = {
     "gss_impair_host": (C.c_int, [C.POINTER(Impair), _P, C.c_uint64, C.c_size_t, C.c_int, _P]),
     "gss_impair_device": (C.c_int, [_P, C.POINTER(Impair), _P, C.c_uint64, C.c_size_t, C.c_int,
                                     _P, _P]),
+    "gss_acq_sizes": (C.c_int, [C.POINTER(Acq), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int32)]),
+    "gss_acquire_host": (C.c_int, [C.POINTER(Acq), _P, _P, _P, C.POINTER(C.c_int), C.c_int]),
+    "gss_acquire_device": (C.c_int, [_P, C.POINTER(Acq), _P, _P, _P, _P, _P]),
+    "gss_acquire": (C.c_int, [_P, C.POINTER(Acq), _P, _P, _P, C.POINTER(C.c_int)]),
+    "gss_acq_expect": (C.c_int, [_P, C.c_double, C.c_int64, C.POINTER(_Truth)]),
+    "gss_acq_threshold": (C.c_double, [C.c_int, C.c_uint64, C.c_double]),
     "gss_dev_timing": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float),
                                  C.POINTER(C.c_float)]),
     "gss_dev_timing_lin": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
@@ -303,6 +357,54 @@ def impair_host(imp, iq, sample0, fmt):
     out = np.zeros(impair_bytes(n, fmt) if fmt in (1, 8, 16) else 0, np.uint8)
     _check(lib().gss_impair_host(C.byref(imp), _ptr(iq), int(sample0), n, int(fmt), _ptr(out)))
     return out
+
+
+def _acq_samples(acq, samples):
+    x = np.ascontiguousarray(samples)
+    if x.nbytes < acq.sample_bytes():
+        raise ValueError(f"the search reads {acq.sample_bytes()} bytes, got {x.nbytes}")
+    return x
+
+
+def acquire_host(acq, samples, want_grid=False, threads=8):
+    """The acquisition search on the host (gss_acquire_host) over samples (any array holding the
+    format's bytes): (peaks ACQ_PEAK_DTYPE [n_prn], grid uint64 [n_prn, 2 K + 1, T] or None,
+    resolved qshift)."""
+    x = _acq_samples(acq, samples)
+    _, T, _, _, P = acq.sizes()
+    peaks = np.zeros(P, ACQ_PEAK_DTYPE)
+    grid = np.zeros((P, 2 * acq.n_half + 1, T), np.uint64) if want_grid else None
+    sh = C.c_int(0)
+    _check(lib().gss_acquire_host(C.byref(acq), _ptr(x), _ptr(peaks), _ptr(grid), C.byref(sh),
+                                  threads))
+    return peaks, grid, sh.value
+
+
+def acq_expect(row, fs, sample_in_block=0):
+    """The labels of one channel row (a CHAN_DTYPE scalar) at a sample of its block
+    (gss_acq_expect): dict(prn, tau [samples], doppler_hz, cn0_offset_db)."""
+    r = np.ascontiguousarray(row, CHAN_DTYPE).reshape(1)
+    t = _Truth()
+    _check(lib().gss_acq_expect(_ptr(r), float(fs), int(sample_in_block), C.byref(t)))
+    return {"prn": t.prn, "tau": t.tau, "doppler_hz": t.doppler_hz,
+            "cn0_offset_db": t.cn0_offset_db}
+
+
+def acq_threshold(n_coh, cells, pfa=1e-3):
+    """the detection threshold on acq_ratio for a search of `cells` cells (gss_acq_threshold)"""
+    return float(lib().gss_acq_threshold(int(n_coh), int(cells), float(pfa)))
+
+
+def acq_ratio(peak):
+    """peak over mean floor of one ACQ_PEAK_DTYPE entry"""
+    return float(peak["peak"]) * float(peak["floor_cnt"]) / float(peak["floor_sum"])
+
+
+def cn0_dbhz(peak, coh_ms=1):
+    """C/N0 estimate [dB-Hz] of one ACQ_PEAK_DTYPE entry: 10 log10((ratio - 1) / coherent time);
+    -inf for a peak not above its floor"""
+    r = acq_ratio(peak)
+    return float(10 * np.log10((r - 1) / (coh_ms * 1e-3))) if r > 1 else float("-inf")
 
 
 def lut():
@@ -775,6 +877,26 @@ class Device:
         _check(lib().gss_impair_device(self._h, C.byref(imp), C.c_void_p(iq_ptr), int(sample0),
                                        int(n), int(fmt), C.c_void_p(out_ptr),
                                        C.c_void_p(stream or None)))
+
+    def acquire(self, acq, samples_ptr, peaks_ptr, grid_ptr=0, qshift_ptr=0, stream=0):
+        """gss_acquire_device: the acquisition search over the samples at device pointer
+        samples_ptr; peaks (n_prn x 32 bytes), the optional grid and resolved shift go to device
+        pointers; async on stream."""
+        _check(lib().gss_acquire_device(self._h, C.byref(acq), C.c_void_p(samples_ptr),
+                                        C.c_void_p(peaks_ptr), C.c_void_p(grid_ptr or None),
+                                        C.c_void_p(qshift_ptr or None),
+                                        C.c_void_p(stream or None)))
+
+    def acquire_from_host(self, acq, samples, want_grid=False):
+        """gss_acquire: acquire() on host samples; returns what acquire_host() returns."""
+        x = _acq_samples(acq, samples)
+        _, T, _, _, P = acq.sizes()
+        peaks = np.zeros(P, ACQ_PEAK_DTYPE)
+        grid = np.zeros((P, 2 * acq.n_half + 1, T), np.uint64) if want_grid else None
+        sh = C.c_int(0)
+        _check(lib().gss_acquire(self._h, C.byref(acq), _ptr(x), _ptr(peaks), _ptr(grid),
+                                 C.byref(sh)))
+        return peaks, grid, sh.value
 
     def run(self, scn, sink, first_block=0, n_blocks=-1, batch=100, threads=8, impair=None):
         """Stream blocks [first_block, first_block + n_blocks) of Scenario scn through gss_run;

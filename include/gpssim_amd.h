@@ -157,7 +157,7 @@ int gss_linearize(const gss_chan_blk_t *blk, const int32_t *nch, int nblk, int n
    gss_run proves with this call the slots of its planner-bound runs (rows ahead, slots of >= 1024
    blocks: the -b 1 runs) and on the host threads the others; GSS_RUN_PROOF=gpu / host / split
    (every other slot on the GPU) forces a mode.  One workgroup per block; a small launch spreads
-   the channels over waves (GSS_PROOF_STRIDE=1 / 16 / 32 / 64 forces the shape, for tests).    */
+   the channels over waves (GSS_PROOF_STRIDE=4 / 16 / 32 forces the shape, for tests).    */
 int gss_linearize_device(gss_dev *d, const gss_chan_blk_t *blk, const int32_t *nch, int nblk,
                          int n_per_blk, const uint32_t *ca_bits, int n_ca, const uint32_t *nav,
                          int n_nav, gss_lin_t *lin, int32_t *fast, void *stream);
@@ -224,6 +224,75 @@ int gss_impair_host(const gss_impair_t *p, const int16_t *iq, uint64_t sample0, 
    uploads the table synchronously).                                                           */
 int gss_impair_device(gss_dev *d, const gss_impair_t *p, const int16_t *iq, uint64_t sample0,
                       size_t n, int fmt, void *out, void *stream);
+
+/* ---- signal acquisition -------------------------------------------------------------------------
+   A measurement of generated samples (an extension; the reference has no receiver): for every
+   selected PRN a search over Doppler bins and code phases, the peak, and the noise floor around
+   it.  Exact integer arithmetic up to the peak table (csrc/common/gss_acq.h):
+     sizes    L = fs coh_ms / 1000 (floor) samples per coherent window, T = ceil(fs / 1000) code
+              phases, N = n_coh L + T - 1 samples read, E = ceil(2 fs / 1023000) + 1
+     wipe     bin k = -n_half..n_half, f_k = k bin_hz: step_k = floor((f_k 2^32 + fs / 2) / fs) mod
+              2^32, idx = ((n step_k) mod 2^32) >> 23, (c, s) = (cos512, sin512)[idx] of gss_lut;
+              yI = xI c + xQ s, yQ = xQ c - xI s
+     quantise q = clamp((y + ((1 << sh) >> 1)) >> sh, -127, 127); sh = qshift, or for -1 the least
+              sh >= 0 with (250 (max|xI| + max|xQ|)) >> sh <= 127 over the N samples
+     replica  r_p[i] = +1 / -1 by chip (i 1023000 / fs) mod 1023 of row p - 1 of gss_ca_table
+     power    P[p][k][tau] = sum_m (S_I^2 + S_Q^2) mod 2^64, S_c = sum_{i < L} q_c[tau + m L + i]
+              r_p[m L + i], 0 <= tau < T
+     peak     the maximum of P per PRN (ties: lowest k, then lowest tau); floor_sum / floor_cnt over
+              the cells of the peak's bin farther than E from it (circular in T)               */
+typedef struct gss_acq {
+    int32_t  fs_hz;              /* sample rate [Hz]                                            */
+    int32_t  fmt;                /* GSS_FMT_SC16 / SC08 / SC01: the file formats                */
+    int32_t  coh_ms;             /* coherent window [ms], >= 1                                  */
+    int32_t  n_coh;              /* M: windows summed non-coherently, 1..1000                   */
+    int32_t  bin_hz;             /* Doppler bin width [Hz], > 0                                 */
+    int32_t  n_half;             /* K: bins -K..K                                               */
+    int32_t  qshift;             /* 0..24, or -1: auto                                          */
+    uint32_t prn_mask;           /* bit p - 1 selects PRN p                                     */
+} gss_acq_t;
+typedef struct gss_acq_peak {
+    uint64_t peak, floor_sum;
+    uint32_t floor_cnt;
+    int32_t  tau, bin, prn;      /* code phase [samples], bin index -K..K, PRN 1..32            */
+} gss_acq_peak_t;                /* 32 bytes; one per selected PRN, ascending PRN               */
+typedef struct gss_acq_truth {   /* what a channel row says the search should find              */
+    double  tau;                 /* code phase [samples] in [0, 1023 / code_step)               */
+    double  doppler_hz;
+    double  cn0_offset_db;       /* 20 log10(gain / 128)                                        */
+    int32_t prn, pad;
+} gss_acq_truth_t;
+
+/* The derived sizes (any pointer may be NULL); GSS_E_ARG for a search gss_acquire_* rejects:
+   L > 2^20, n_coh > 1000, T <= 2 E + 1, an empty prn_mask, or a field out of its range.  A
+   bin_hz above 500 / coh_ms leaves Doppler holes: accepted, with gss_last_error() set.        */
+int gss_acq_sizes(const gss_acq_t *a, int32_t *L, int32_t *T, int64_t *N, int32_t *E,
+                  int32_t *n_prn);
+/* The search on the host (the reference statement): samples = N samples of a->fmt (SC01: from
+   the MSB of the first byte), peaks [n_prn], grid NULL or [n_prn][2 K + 1][T], qshift_out NULL
+   or the resolved shift.                                                                      */
+int gss_acquire_host(const gss_acq_t *a, const void *samples, gss_acq_peak_t *peaks,
+                     uint64_t *grid, int *qshift_out, int threads);
+/* The same on the device: device pointers (d_grid, d_qshift may be NULL), asynchronous on stream,
+   samples 2-byte aligned (SC08 / SC01: 1-byte).  Scratch (the wiped planes, the replicas and,
+   without d_grid, the power rows) is kept per device and grows on first use, synchronously; one
+   search per device may be in flight.  GSS_ACQ_PATH=valu takes the plain integer correlator
+   instead of the matrix cores (same outputs).                                                 */
+int gss_acquire_device(gss_dev *d, const gss_acq_t *a, const void *d_samples,
+                       gss_acq_peak_t *d_peaks, uint64_t *d_grid, int32_t *d_qshift,
+                       void *stream);
+/* gss_acquire_device from host buffers: uploads, searches, downloads, synchronises.           */
+int gss_acquire(gss_dev *d, const gss_acq_t *a, const void *samples, gss_acq_peak_t *peaks,
+                uint64_t *grid, int *qshift_out);
+/* The labels of one channel row at sample `sample_in_block` of its block: code phase tau =
+   ((1023 - code) / code_step) mod (1023 / code_step) with code = code0 + sample code_step,
+   Doppler carr_step fs, and the level offset of its gain.                                     */
+int gss_acq_expect(const gss_chan_blk_t *row, double fs, int64_t sample_in_block,
+                   gss_acq_truth_t *out);
+/* The detection threshold on ratio = peak floor_cnt / floor_sum: x / M where e^-x sum_{j < M}
+   x^j / j! = pfa / cells (the maximum of `cells` noise-only cells of M summed windows exceeds it
+   with probability about pfa).  NaN on bad arguments.                                         */
+double gss_acq_threshold(int M, uint64_t cells, double pfa);
 
 /* Kernel timing from HIP events recorded on the launch stream around every Stage A and Stage B
    launch (gss_synth_device, gss_anchor_device, gss_render_device; rings of the last 256 of
