@@ -30,6 +30,33 @@
  * rendered: 12.5 vs 13.4 GS/s, profiles/round3/ablate_r3n.log).  NCOPY = 2 alternates slots over
  * two copy streams (two DMA engines on the link; measured slower, same log).  A slot's device
  * output buffer is rewritten only after its own D2H (event).
+ *
+ * Two more threads where the planner is the limit.  The rows thread owns the
+ * scenario during the run: next_ask's batches (gss_scn_next_deferred) with the nav rows and
+ * sources new with each, a batch ahead of the planner, on its own worker pool; the planner keeps
+ * the slot carriers and host copies of the nav table.  The prover thread takes the slots' host
+ * proofs in slot order on its own pool: planner -> PROVING -> prover -> PLANNED -> main.
+ *
+ * The environment switches, read once per run (gss_run_modes.h: run_env_read) and resolved in a
+ * fixed order into the run's modes (run_modes_resolve, with the measurements behind the defaults).
+ * T: a test switch, M: a measurement switch; the others select a supported arrangement.
+ *   switch                 values (default)           selects
+ *   GSS_PATH               walk (fast)                walk: every block on the exact path, no proofs
+ *   GSS_RUN_SPEC           0 (1)                      0: the carrier chain walked on the host
+ *   GSS_RUN_REC            0 (1)                      0: the walks, not their records, come back
+ *   GSS_RUN_ANCHORS        0 (1)                   M  0: the walks that come back anchor no proofs
+ *   GSS_RUN_DEV_ANCHORS    1 (0)                   M  1: GPU proofs anchored on the device walks
+ *   GSS_RUN_ROWS_AHEAD     0, 1 (slots >= 1024)       the rows thread
+ *   GSS_RUN_ROWS_POOL      0 (1)                   M  0: the rows thread on the planner's worker pool
+ *   GSS_RUN_PROOF          host, gpu, split (auto)    where the proofs run; split: every other slot
+ *   GSS_RUN_PROVER         0 (1)                   M  0: host proofs on the planner thread
+ *   GSS_RUN_UPLOAD         dma (kernel)            M  dma: the slots' inputs by the copy engine
+ *   GSS_RUN_SPEC_CUS       N (0)                   M  the walks' stream on N of the device's CUs
+ *   GSS_RUN_RENDER_REST    set (unset)             M  with SPEC_CUS: the render stream on the others
+ *   GSS_RUN_FORCE_EXACT    k (0)                   T  every k-th block of the run to the exact path
+ *   GSS_RUN_LATE_VERDICTS  1 (0)                   T  the GPU proofs' rejects always redone in drain
+ *   GSS_RUN_TRACE          1 (0)                   M  timestamps on stderr; cached per process
+ * Compile-time: GSS_RUN_NCOPY (1), GSS_RUN_DEPTH (2), GSS_RUN_AHEAD (2).
  */
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -44,6 +71,7 @@
 #include <unordered_map>
 #include <vector>
 #include "gpssim_amd.h"
+#include "gss_run_modes.h"
 
 extern "C" int gss_fail(int code, const char *fmt, ...);
 extern "C" void gss_pool_select(int id);             /* pool.c */
@@ -355,21 +383,21 @@ struct Slot {
 };
 
 struct Run {
+    explicit Run(const RunModes &modes) : m(modes) {}
+    const RunModes m;                /* the run's modes (gss_run_modes.h), fixed at its start */
+    /* the run's context, set once (gss_run_ex, run_alloc) */
     gss_scn *scn;
-    int batch, threads, n_per_blk, use_lin, carrier_int;
-    int proof_mode = 0;              /* 0: host proofs, 1: all on the GPU, 2: every other slot */
-    int gpu_proof = 0;               /* any proofs on the GPU (gss_proof.hip), run ahead by the
-                                        planner on each slot's own stream (proof_ahead)        */
-    hipStream_t nav_st = nullptr;    /* ... the planner's stream for the slots' nav rows      */
+    gss_dev *dev = nullptr;
+    int ordinal = 0;                 /* the device's ordinal (the buffer pool's key)          */
+    int batch, threads, n_per_blk, carrier_int;
+    int fmt = 0;                     /* the format the blocks render at                        */
+    size_t bb = 0, bb_r = 0;         /* bytes per block: to the sink, rendered                 */
+    hipStream_t st = nullptr;        /* the compute stream                                     */
+    hipStream_t cp[NCOPY] = {};      /* the copy streams                                       */
+    uint32_t *d_ca = nullptr;        /* the run's device C/A table                            */
+    hipStream_t nav_st = nullptr;    /* GPU proofs: the planner's stream for the slots' nav rows */
     hipEvent_t t_base = nullptr;     /* GSS_RUN_TRACE: the GPU clock's origin (compute stream) */
     hipEvent_t ca_ready = nullptr;   /* GPU proofs: the device C/A table is built (compute stream) */
-    int upload_dev = 1;              /* uploads by kernel (h2d); GSS_RUN_UPLOAD=dma: copy engine */
-    const uint32_t *d_ca = nullptr;  /* the run's device C/A table                            */
-    int force_exact;                 /* GSS_RUN_FORCE_EXACT=k: every k-th block to the exact
-                                        path (tests of the mixed batch), 0 = off */
-    int late_verdicts = 0;           /* GSS_RUN_LATE_VERDICTS=1 (tests): submit_proven treats every
-                                        GPU proof as still running, so rejected blocks always take
-                                        the redo path in drain (redo_rejected)            */
     int64_t first, last;             /* [first, last) block range of the run */
     int64_t start = 0;               /* the handle's next block when the run began (an earlier
                                         run, a seek): the planner's and rows thread's cursor   */
@@ -397,7 +425,7 @@ struct Run {
         std::vector<gss_chain_t> chain;
         gss_spec_in_t *h_in = nullptr;        /* pinned host, read and written by the lanes */
         gss_spec_t *h_spec = nullptr;
-        /* records mode (r.rec): the walks and guesses stay on the device (d_in, d_spec) and
+        /* records mode (r.m.rec): the walks and guesses stay on the device (d_in, d_spec) and
            only each row's record comes back (h_rec, pinned) */
         gss_spec_in_t *d_in = nullptr;
         gss_spec_t *d_spec = nullptr;
@@ -426,25 +454,25 @@ struct Run {
         int nb = 0, end = 0, err = 0, ready = 0;
         double t0 = 0.0, t1 = 0.0;                           /* trace: production start, end */
     } rb[2];
-    int rows_ahead = 0, rb_take = 0, rows_done = 0;
-    int prover = 0;                  /* proofs on their own thread (rows_ahead, fast path): the
-                                        planner hands slots over PROVING */
+    int rb_take = 0, rows_done = 0;
     double carr[GSS_MAXCH];          /* rows_ahead: the slot carriers at the planner's next batch */
     std::vector<gss_nav_src_t> nav_src_h;
     std::vector<uint32_t> nav_rows_h;
-    gss_dev *dev = nullptr;
-    int spec = 0;                    /* per batch (gss_run), or over the range (hand-off)      */
-    int rec = 0;                     /* per batch: records, not walks, back from the GPU
-                                        (gss_spec_records_device; GSS_RUN_REC=0: the walks)    */
-    int dev_anch = 0;                /* records mode: GPU proofs take their anchors from the
-                                        batch's device walks (GSS_RUN_DEV_ANCHORS=1).  Off: the
-                                        configs[4] run measured 43.2-43.4 GB/s with them against
-                                        43.8-44.8 without (profiles/round5/e2e/probe_r5s)      */
-    hipStream_t spec_st = nullptr;
+    hipStream_t spec_st = nullptr;   /* the walks' stream (high priority)                      */
     uint64_t *spec_warm = nullptr;   /* device scratch of the walks' first launch (one row) */
     int64_t spec_rows = 0, spec_hits = 0;
     Slot slot[NSLOT];
 };
+
+/* a field of the run's shared state set under its mutex, and the waiters woken */
+static void post(Run &r, int &field, int v)
+{
+    {
+        std::lock_guard<std::mutex> lk(r.mu);
+        field = v;
+    }
+    r.cv.notify_all();
+}
 
 size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 /* the walks' warm-up scratch (one row): in, its device copy, the walk, the record */
@@ -458,7 +486,7 @@ static_assert(sizeof(gss_spec_rec_t) <= 128, "the record fits its warm-up slot")
    walked without them (a third cheaper: no partial-cycle walks to the 8 checkpoint positions)
    and they are computed afterwards for the uncertified blocks only, from each row's carr0 by
    the same exact walk.  The integer-carrier chain records them for free and keeps doing so. */
-static bool lazy_ck(const Run &r) { return r.use_lin && !r.carrier_int; }
+static bool lazy_ck(const Run &r) { return r.m.use_lin && !r.carrier_int; }
 
 /* Uploads of the slots' inputs (rows, lines, checkpoints, nav sources: ~10 MB per 2048-block
    slot) by a kernel reading the pinned host buffers directly, not by the copy engine
@@ -476,7 +504,7 @@ static int dev_copy(void *dst, const void *src, size_t n, hipStream_t st)
 /* host buffer (pinned) to device, stream-ordered on st */
 static int h2d(const Run &r, void *dst, const void *src, size_t n, hipStream_t st)
 {
-    if (n == 0 || r.upload_dev)
+    if (n == 0 || r.m.upload_dev)
         return dev_copy(dst, src, n, st);
     return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st) == hipSuccess
                ? 0 : gss_fail(GSS_E_HIP, "upload of %zu B", n);
@@ -495,18 +523,20 @@ int run_proof_launch(const gss_chan_blk_t *blk, const int32_t *nch, int nblk, in
                      int force_exact, hipStream_t st);            /* gss_proof.hip */
 namespace {
 
-static void fill_fb_ck(const Run &r, Slot &sl)
+/* the exact-path block list fast[nb..] from the verdicts fast[0..nb): the blocks the proof
+   rejected, in order; sets and returns its length (sl.n_fb) */
+static int list_exact(Slot &sl)
 {
-    if (r.force_exact > 0) {
-        for (int i = 0; i < sl.nb; i++)
-            if ((sl.first + i) % r.force_exact == 0)
-                sl.fast[i] = 0;
-        int nf = 0;
-        for (int i = 0; i < sl.nb; i++)
-            if (!sl.fast[i])
-                sl.fast[sl.nb + nf++] = i;
-        sl.n_fb = nf;
-    }
+    int nf = 0;
+    for (int b = 0; b < sl.nb; b++)
+        if (!sl.fast[b])
+            sl.fast[sl.nb + nf++] = b;
+    return sl.n_fb = nf;
+}
+
+/* the listed blocks' lazy checkpoints, from their rows' exact carriers (see lazy_ck) */
+static void fill_lazy_ck(const Run &r, Slot &sl)
+{
     if (!lazy_ck(r))
         return;
     for (int i = 0; i < sl.n_fb; i++) {
@@ -517,6 +547,33 @@ static void fill_fb_ck(const Run &r, Slot &sl)
                                       sl.ck + e * GSS_NCK);
         }
     }
+}
+
+/* The host proof of a slot (planner or prover thread): its certified lines and verdicts against
+   the nav table (nav, n_nav rows), the exact-path list, its checkpoints.  force_exact is applied
+   here only: the GPU proof takes it as an argument (proof_ahead). */
+static int prove_host(const Run &r, Slot &sl, const uint32_t *nav, int n_nav)
+{
+    const int rc = gss_linearize_ex(sl.blk, sl.nch, sl.nb, r.n_per_blk, r.ca, 32, nav, n_nav,
+                                    sl.has_anch ? sl.anch : nullptr, sl.lin, sl.fast, r.threads);
+    if (rc)
+        return rc;
+    if (r.m.force_exact > 0)
+        for (int i = 0; i < sl.nb; i++)
+            if ((sl.first + i) % r.m.force_exact == 0)
+                sl.fast[i] = 0;
+    list_exact(sl);
+    fill_lazy_ck(r, sl);
+    return 0;
+}
+
+/* the most channels of any of nb blocks (at least 1) */
+static int nch_max_of(const int32_t *nch, int nb)
+{
+    int m = 1;
+    for (int i = 0; i < nb; i++)
+        m = nch[i] > m ? nch[i] : m;
+    return m;
 }
 
 /* The up-front range's chain run ahead on the GPU, in chunks of 4,096 blocks: each chunk's
@@ -718,7 +775,7 @@ int plan_range_upfront(Run &r)
     if (rc)
         return rc;
     /* the speculated chain: with a prediction callback and the walks on the GPU */
-    const bool speculate = r.opts->carr_predict && r.spec && r.rec;
+    const bool speculate = r.opts->carr_predict && r.m.spec && r.m.rec;
     /* a prediction callback this rank will not use (GSS_RUN_SPEC=0, GSS_RUN_REC=0, the exact
        path): round -1 tells the ranks after it not to wait for its maps */
     if (r.opts->carr_predict && !speculate &&
@@ -750,19 +807,12 @@ int plan_range_upfront(Run &r)
     double carr[GSS_MAXCH];
     if (!lazy_ck(r))
         r.pre_ck.resize((size_t)r.pre_n * GSS_MAXCH * GSS_NCK);
-    if (speculate) {
+    if (speculate)                                     /* (takes carr_in itself, late) */
         rc = chain_upfront_speculated(r, chain.data(), start0, carr);
-        if (rc)
-            return rc;
-        if (r.opts->carr_out && r.opts->carr_out(r.opts->carr_user, carr))
-            return gss_fail(GSS_E_IO, "carrier hand-off (out) failed after block %lld",
-                            (long long)(r.first + r.pre_n - 1));
-        return 0;
-    }
-    if (r.opts->carr_in(r.opts->carr_user, carr))
+    else if (r.opts->carr_in(r.opts->carr_user, carr))
         return gss_fail(GSS_E_IO, "carrier hand-off (in) failed at block %lld",
                         (long long)r.first);
-    if (r.spec)                                        /* the chain run ahead on the GPU */
+    else if (r.m.spec)                                 /* the chain run ahead on the GPU */
         rc = chain_upfront_spec(r, carr, chain.data());
     else
         rc = gss_carr_chain(carr, r.pre_blk.data(), r.pre_nch.data(), chain.data(),
@@ -782,7 +832,7 @@ int take_nav_sources(Run &r, Slot &sl, int upto)
 {
     const gss_nav_src_t *src = nullptr;
     int n_all = 0;
-    if (r.rows_ahead) {
+    if (r.m.rows_ahead) {
         src = r.nav_src_h.data();
         n_all = (int)r.nav_src_h.size();
     } else {
@@ -857,10 +907,7 @@ int next_ask(const Run &r, int64_t cursor);
 
 void rows_thread(Run *r)
 {
-    {
-        const char *e = getenv("GSS_RUN_ROWS_POOL");   /* 0: share the planner's workers */
-        gss_pool_select(e && e[0] == '0' ? 0 : 1);
-    }
+    gss_pool_select(r->m.rows_pool ? 1 : 0);           /* 0: share the planner's workers */
     int64_t cursor = r->start;
     int nav_done = 0;
     for (int i = 0;; i++) {
@@ -899,19 +946,11 @@ void rows_thread(Run *r)
         q.end = rc || nb == 0;
         cursor += nb;
         q.t1 = trace_on() ? tnow() : 0.0;
-        {
-            std::lock_guard<std::mutex> lk(r->mu);
-            q.ready = 1;
-        }
-        r->cv.notify_all();
+        post(*r, q.ready, 1);
         if (q.end)
             break;
     }
-    {
-        std::lock_guard<std::mutex> lk(r->mu);
-        r->rows_done = 1;
-    }
-    r->cv.notify_all();
+    post(*r, r->rows_done, 1);
 }
 
 /* the next batch of rows_ahead into b (vectors swapped, no copy); its nav rows and sources onto
@@ -951,11 +990,7 @@ int take_rows(Run &r, Run::SpecBatch &b, int *nb_out)
     if (trace_on())
         fprintf(stderr, "trace rows nb %d produced %.6f %.6f wait %.6f\n", q.nb, q.t0, q.t1,
                 tnow() - tw);
-    {
-        std::lock_guard<std::mutex> lk(r.mu);
-        q.ready = 0;
-    }
-    r.cv.notify_all();
+    post(r, q.ready, 0);
     r.rb_take ^= 1;
     return 0;
 }
@@ -965,7 +1000,7 @@ int spec_launch(Run &r, Run::SpecBatch &b, int ask)
     b.nb = 0;
     b.launched = 1;
     int rc = 0, nb = 0;
-    if (r.rows_ahead) {
+    if (r.m.rows_ahead) {
         /* the finished batches' exact carriers, carried by the lines through the batch still in
            flight (if any): a prediction, ~3e-10 cycle off, which only the guesses use */
         memcpy(b.carr, r.carr, sizeof b.carr);
@@ -1001,7 +1036,7 @@ int spec_launch(Run &r, Run::SpecBatch &b, int ask)
         RUN_TRY(hipStreamWaitEvent(r.spec_st, b.consumed, 0));
         b.consumed_pending = 0;
     }
-    rc = r.rec ? gss_spec_records_device(r.dev, b.h_in, nrow, r.n_per_blk, b.d_in, b.d_spec,
+    rc = r.m.rec ? gss_spec_records_device(r.dev, b.h_in, nrow, r.n_per_blk, b.d_in, b.d_spec,
                                          b.h_rec, r.spec_st)
                : gss_spec_device(r.dev, b.h_in, nrow, r.n_per_blk, b.h_spec, r.spec_st);
     if (rc)
@@ -1025,16 +1060,16 @@ int spec_finish(Run &r, Run::SpecBatch &b, gss_chan_blk_t *blk, int32_t *nch, in
     RUN_TRY(hipEventSynchronize(b.walked));
     const double t0 = trace_on() ? tnow() : 0.0;
     double carr[GSS_MAXCH];                          /* exact: the batches before are done */
-    memcpy(carr, r.rows_ahead ? r.carr : b.carr, sizeof carr);
+    memcpy(carr, r.m.rows_ahead ? r.carr : b.carr, sizeof carr);
     int hit = 0;
-    int rc = r.rec ? gss_carr_chain_records(carr, b.blk.data(), b.nch.data(), b.chain.data(), nb,
+    int rc = r.m.rec ? gss_carr_chain_records(carr, b.blk.data(), b.nch.data(), b.chain.data(), nb,
                                             r.n_per_blk, b.h_rec, r.threads, &hit)
                    : gss_carr_chain_anchored(carr, b.blk.data(), b.nch.data(), b.chain.data(),
                                              nb, r.n_per_blk, b.h_in, b.h_spec, r.threads, &hit,
                                              anch);
     if (rc)
         return rc;
-    if (r.rows_ahead)
+    if (r.m.rows_ahead)
         memcpy(r.carr, carr, sizeof carr);             /* the scenario is the rows thread's */
     else
         rc = gss_scn_set_carrier(r.scn, carr);
@@ -1083,25 +1118,13 @@ int plan_into(Run &r, Slot &sl, int64_t *cursor)
             return 0;
         }
         sl.nb = nb;
-        int m = 1;
-        for (int i = 0; i < nb; i++)
-            m = sl.nch[i] > m ? sl.nch[i] : m;
-        sl.nch_max = m;
+        sl.nch_max = nch_max_of(sl.nch, nb);
         sl.n_fb = 0;
-        if (r.use_lin && !sl.gpu_proven) {
+        if (r.m.use_lin && !sl.gpu_proven) {
             const uint32_t *rows = nullptr;
             int n_rows = 0;
             gss_scn_nav_table(r.scn, &rows, &n_rows);
-            rc = gss_linearize(sl.blk, sl.nch, nb, r.n_per_blk, r.ca, 32, rows, n_rows,
-                               sl.lin, sl.fast, r.threads);
-            if (rc)
-                return rc;
-            int nf = 0;
-            for (int i = 0; i < nb; i++)
-                if (!sl.fast[i])
-                    sl.fast[nb + nf++] = i;
-            sl.n_fb = nf;
-            fill_fb_ck(r, sl);
+            return prove_host(r, sl, rows, n_rows);
         }
         return 0;
     }
@@ -1109,7 +1132,7 @@ int plan_into(Run &r, Slot &sl, int64_t *cursor)
         const int ask = next_ask(r, *cursor);
         int nb = 0;
         int rc = 0;
-        if (r.rows_ahead) {
+        if (r.m.rows_ahead) {
             /* two batches' walks in flight: the oldest is finished (its chain, exact) while the
                next one's walks run on the GPU; the batch after that is launched first */
             while (!rc && r.n_fly < 2 && !r.fly_end) {
@@ -1131,7 +1154,7 @@ int plan_into(Run &r, Slot &sl, int64_t *cursor)
                 r.sb_head = (r.sb_head + 1) % 3;
                 r.n_fly--;
             }
-        } else if (r.spec) {
+        } else if (r.m.spec) {
             Run::SpecBatch &b = r.sb[r.sb_cur];
             if (!b.launched && ask > 0)
                 rc = spec_launch(r, b, ask);
@@ -1163,14 +1186,11 @@ int plan_into(Run &r, Slot &sl, int64_t *cursor)
             continue;                                  /* before the range: planned, dropped */
         sl.first = b0;
         sl.nb = nb;
-        sl.has_anch = sl.anch != nullptr && r.spec && !r.rec;
-        int m = 1;
-        for (int i = 0; i < nb; i++)
-            m = sl.nch[i] > m ? sl.nch[i] : m;
-        sl.nch_max = m;
+        sl.has_anch = sl.anch != nullptr && r.m.spec && !r.m.rec;
+        sl.nch_max = nch_max_of(sl.nch, nb);
         const uint32_t *rows = nullptr;
         int n_rows = 0;
-        if (r.rows_ahead) {
+        if (r.m.rows_ahead) {
             rows = r.nav_rows_h.data();
             n_rows = (int)(r.nav_rows_h.size() / GSS_NAV_WORDS);
         } else {
@@ -1179,25 +1199,16 @@ int plan_into(Run &r, Slot &sl, int64_t *cursor)
         rc = take_nav_sources(r, sl, n_rows);          /* the GPU builds the new rows */
         if (rc)
             return rc;
-        if (r.prover) {                                /* the proofs, on the prover thread */
+        if (r.m.prover) {                                /* the proofs, on the prover thread */
             sl.lin_nav = rows;
             sl.lin_n_nav = n_rows;
             return 0;
         }
         sl.n_fb = 0;
-        if (r.use_lin && !sl.gpu_proven) {             /* the proofs, on the planner thread */
+        if (r.m.use_lin && !sl.gpu_proven) {             /* the proofs, on the planner thread */
             if (trace_on())
                 fprintf(stderr, "trace scn_done %.6f\n", tnow());
-            rc = gss_linearize_ex(sl.blk, sl.nch, nb, r.n_per_blk, r.ca, 32, rows, n_rows,
-                                  sl.has_anch ? sl.anch : nullptr, sl.lin, sl.fast, r.threads);
-            if (rc)
-                return rc;
-            int nf = 0;
-            for (int i = 0; i < nb; i++)
-                if (!sl.fast[i])
-                    sl.fast[nb + nf++] = i;
-            sl.n_fb = nf;
-            fill_fb_ck(r, sl);
+            return prove_host(r, sl, rows, n_rows);
         }
         return 0;
     }
@@ -1218,9 +1229,9 @@ void planner(Run *r)
                 return;
         }
         const double t0 = trace_on() ? tnow() : 0.0;
-        sl.gpu_proven = r->use_lin && (r->proof_mode == 1 || (r->proof_mode == 2 && (i & 1)));
+        sl.gpu_proven = r->m.use_lin && (r->m.proof_mode == 1 || (r->m.proof_mode == 2 && (i & 1)));
         int rc = up_rc ? up_rc : plan_into(*r, sl, &cursor);
-        if (!rc && !sl.end && r->gpu_proof)
+        if (!rc && !sl.end && r->m.gpu_proof)
             rc = proof_ahead(*r, sl);
         if (trace_on())
             fprintf(stderr, "trace plan slot %d nb %d %.6f %.6f\n", i % NSLOT, sl.nb, t0, tnow());
@@ -1230,7 +1241,7 @@ void planner(Run *r)
                 sl.err = rc;
                 sl.end = 1;
             }
-            sl.state = r->prover ? PROVING : PLANNED;
+            sl.state = r->m.prover ? PROVING : PLANNED;
         }
         r->cv.notify_all();
         if (sl.end)
@@ -1238,7 +1249,7 @@ void planner(Run *r)
     }
 }
 
-/* The slots' proofs in slot order (r.prover): gss_linearize on this thread's own worker pool,
+/* The slots' proofs in slot order (r.m.prover): gss_linearize on this thread's own worker pool,
    the exact-path block list and its checkpoints, then the slot goes to the main thread. */
 void prover(Run *r)
 {
@@ -1253,29 +1264,16 @@ void prover(Run *r)
         }
         const double t0 = trace_on() ? tnow() : 0.0;
         if (!sl.end && !sl.err && !sl.gpu_proven) {
-            int rc = gss_linearize_ex(sl.blk, sl.nch, sl.nb, r->n_per_blk, r->ca, 32, sl.lin_nav,
-                                      sl.lin_n_nav, sl.has_anch ? sl.anch : nullptr, sl.lin,
-                                      sl.fast, r->threads);
+            const int rc = prove_host(*r, sl, sl.lin_nav, sl.lin_n_nav);
             if (rc) {
                 sl.err = rc;
                 sl.end = 1;
-            } else {
-                int nf = 0;
-                for (int b = 0; b < sl.nb; b++)
-                    if (!sl.fast[b])
-                        sl.fast[sl.nb + nf++] = b;
-                sl.n_fb = nf;
-                fill_fb_ck(*r, sl);
             }
         }
         if (trace_on())
             fprintf(stderr, "trace prove slot %d nb %d %.6f %.6f\n", i % NSLOT, sl.nb, t0, tnow());
         const int end = sl.end;
-        {
-            std::lock_guard<std::mutex> lk(r->mu);
-            sl.state = PLANNED;
-        }
-        r->cv.notify_all();
+        post(*r, sl.state, PLANNED);
         if (end)
             return;
     }
@@ -1296,7 +1294,7 @@ size_t nav_rows_bound(const gss_scn *s, const gss_scn_info_t &info)
 }
 
 /* the device nav table holds at least `rows` rows (grown on the compute stream's order) */
-int nav_reserve(Run &r, size_t rows, hipStream_t st)
+int nav_reserve(Run &r, size_t rows)
 {
     if (rows <= r.d_nav_cap)
         return 0;
@@ -1306,7 +1304,7 @@ int nav_reserve(Run &r, size_t rows, hipStream_t st)
     uint32_t *p = nullptr;
     RUN_TRY(dev_alloc((void **)&p, sizeof(uint32_t) * GSS_NAV_WORDS * cap));
     if (r.d_nav) {
-        RUN_TRY(hipStreamSynchronize(st));             /* earlier slots' kernels read it */
+        RUN_TRY(hipStreamSynchronize(r.st));           /* earlier slots' kernels read it */
         RUN_TRY(hipMemcpy(p, r.d_nav, sizeof(uint32_t) * GSS_NAV_WORDS * r.d_nav_cap,
                           hipMemcpyDeviceToDevice));
         dev_free(r.d_nav);
@@ -1330,26 +1328,41 @@ struct SlotDev {
 
 SlotDev slot_dev(const Slot &sl)
 {
-    const size_t s_blk = sizeof(gss_chan_blk_t) * GSS_MAXCH * (size_t)sl.nb;
-    const size_t s_nch = sizeof(int32_t) * (size_t)sl.nb;
-    const size_t s_ck = sizeof(double) * GSS_MAXCH * GSS_NCK * (size_t)sl.nb;
-    const size_t s_nav = sizeof(gss_nav_src_t) * (size_t)(sl.n_nav > 0 ? sl.n_nav : 1);
-    const size_t s_lin = sl.lin ? sizeof(gss_lin_t) * GSS_MAXCH * (size_t)sl.nb : 0;
-    const size_t s_fast = sl.lin ? sizeof(int32_t) * 2 * (size_t)sl.nb : 0;
-    const int anch = sl.has_anch && sl.gpu_proven;
-    const size_t s_anch = anch ? sizeof(gss_carr_anchor_t) * GSS_MAXCH * (size_t)sl.nb : 0;
+    const size_t nb = (size_t)sl.nb, rows = GSS_MAXCH * nb;
+    size_t off = 0;                                    /* each part 256-byte aligned */
+    auto take = [&](size_t bytes) {
+        uint8_t *p = sl.d_in + off;
+        off += al256(bytes);
+        return (void *)p;
+    };
     SlotDev v;
-    v.need = al256(s_blk) + al256(s_nch) + al256(s_ck) + al256(s_nav) + al256(s_lin) +
-             al256(s_fast) + al256(s_anch);
-    uint8_t *p = sl.d_in;
-    v.blk = (gss_chan_blk_t *)p;
-    v.nch = (int32_t *)(p + al256(s_blk));
-    v.ck = (double *)(p + al256(s_blk) + al256(s_nch));
-    v.src = (gss_nav_src_t *)(p + al256(s_blk) + al256(s_nch) + al256(s_ck));
-    v.lin = (gss_lin_t *)((uint8_t *)v.src + al256(s_nav));
-    v.fast = (int32_t *)((uint8_t *)v.lin + al256(s_lin));
-    v.anch = anch ? (gss_carr_anchor_t *)((uint8_t *)v.fast + al256(s_fast)) : nullptr;
+    v.blk = (gss_chan_blk_t *)take(sizeof(gss_chan_blk_t) * rows);
+    v.nch = (int32_t *)take(sizeof(int32_t) * nb);
+    v.ck = (double *)take(sizeof(double) * GSS_NCK * rows);
+    v.src = (gss_nav_src_t *)take(sizeof(gss_nav_src_t) * (size_t)(sl.n_nav > 0 ? sl.n_nav : 1));
+    v.lin = (gss_lin_t *)take(sl.lin ? sizeof(gss_lin_t) * rows : 0);
+    v.fast = (int32_t *)take(sl.lin ? sizeof(int32_t) * 2 * nb : 0);
+    v.anch = sl.has_anch && sl.gpu_proven
+                 ? (gss_carr_anchor_t *)take(sizeof(gss_carr_anchor_t) * rows) : nullptr;
+    v.need = off;
     return v;
+}
+
+/* sl.d_in holds the slot's inputs (slot_dev(sl).need), grown if it must; busy: the stream whose
+   earlier work may still read the old buffer (synchronised first), or null */
+int slot_in_reserve(Slot &sl, hipStream_t busy)
+{
+    const size_t need = slot_dev(sl).need;
+    if (need <= sl.d_in_cap)
+        return 0;
+    if (busy)
+        RUN_TRY(hipStreamSynchronize(busy));
+    dev_free(sl.d_in);
+    sl.d_in = nullptr;
+    sl.d_in_cap = 0;
+    RUN_TRY(dev_alloc((void **)&sl.d_in, need));
+    sl.d_in_cap = need;
+    return 0;
 }
 
 /* Additive noise: blocks [b0, b0 + nblk) of the slot, rendered at SC16 into d_out, through the
@@ -1378,14 +1391,9 @@ int proof_ahead(Run &r, Slot &sl)
 {
     /* the nav rows of every slot come from here when any slot is proven on the GPU (a row may
        continue one that an earlier slot brought); the proof only for the slots that take it */
-    const size_t need = slot_dev(sl).need;
-    if (need > sl.d_in_cap) {                          /* the slot is FREE: nothing reads it */
-        dev_free(sl.d_in);
-        sl.d_in = nullptr;
-        sl.d_in_cap = 0;
-        RUN_TRY(dev_alloc((void **)&sl.d_in, need));
-        sl.d_in_cap = need;
-    }
+    int rc = slot_in_reserve(sl, nullptr);             /* the slot is FREE: nothing reads it */
+    if (rc)
+        return rc;
     const SlotDev v = slot_dev(sl);
     const int n_rows = sl.nav_first + sl.n_nav;
     if ((size_t)n_rows > r.d_nav_cap)
@@ -1393,7 +1401,7 @@ int proof_ahead(Run &r, Slot &sl)
                         r.d_nav_cap);
     if (sl.n_nav > 0) {
         RUN_H2D(v.src, sl.nav, sizeof(gss_nav_src_t) * (size_t)sl.n_nav, r.nav_st);
-        int rc = gss_nav_rows_device(r.dev, v.src, sl.nav_first, sl.n_nav, r.d_nav, r.nav_st);
+        rc = gss_nav_rows_device(r.dev, v.src, sl.nav_first, sl.n_nav, r.d_nav, r.nav_st);
         if (rc)
             return rc;
     }
@@ -1407,12 +1415,12 @@ int proof_ahead(Run &r, Slot &sl)
     if (v.anch)
         RUN_H2D(v.anch, sl.anch, sizeof(gss_carr_anchor_t) * GSS_MAXCH * (size_t)sl.nb, sl.pst);
     RUN_TRY(hipStreamWaitEvent(sl.pst, sl.navd, 0));
-    Run::SpecBatch *sb = r.rec && r.dev_anch && sl.sb_idx >= 0 && !v.anch ? &r.sb[sl.sb_idx]
+    Run::SpecBatch *sb = r.m.rec && r.m.dev_anch && sl.sb_idx >= 0 && !v.anch ? &r.sb[sl.sb_idx]
                                                                           : nullptr;
-    int rc = run_proof_launch(v.blk, v.nch, sl.nb, r.n_per_blk, r.d_ca, 32, r.d_nav,
-                              n_rows > 0 ? n_rows : 1, v.anch, sb ? sb->d_in : nullptr,
-                              sb ? sb->d_spec : nullptr, v.lin, v.fast, sl.first, r.force_exact,
-                              sl.pst);
+    rc = run_proof_launch(v.blk, v.nch, sl.nb, r.n_per_blk, r.d_ca, 32, r.d_nav,
+                          n_rows > 0 ? n_rows : 1, v.anch, sb ? sb->d_in : nullptr,
+                          sb ? sb->d_spec : nullptr, v.lin, v.fast, sl.first, r.m.force_exact,
+                          sl.pst);
     if (rc)
         return rc;
     if (sb) {                                /* the batch's next walks wait for this proof */
@@ -1427,11 +1435,30 @@ int proof_ahead(Run &r, Slot &sl)
     return 0;
 }
 
+/* The rendered slot to the host: once the compute stream's work so far is done (rendered), the
+   copy stream cp takes its bytes, its status and, with GPU proofs, the verdicts (d_verdicts, or
+   null) into the pinned buffers, then records done */
+int slot_download(Run &r, Slot &sl, hipStream_t cp, const int32_t *d_verdicts)
+{
+    RUN_TRY(hipEventRecord(sl.rendered, r.st));
+    RUN_TRY(hipStreamWaitEvent(cp, sl.rendered, 0));
+    if (sl.tc)
+        RUN_TRY(hipEventRecord(sl.tc, cp));
+    RUN_TRY(hipMemcpyAsync(sl.h_out, slot_bytes(sl), r.bb * (size_t)sl.nb, hipMemcpyDeviceToHost,
+                           cp));
+    RUN_TRY(hipMemcpyAsync(sl.h_status, sl.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, cp));
+    if (d_verdicts)
+        RUN_TRY(hipMemcpyAsync(sl.fast, d_verdicts, sizeof(int32_t) * (size_t)sl.nb,
+                               hipMemcpyDeviceToHost, cp));
+    RUN_TRY(hipEventRecord(sl.done, cp));
+    return 0;
+}
+
 /* submit for a slot proven by proof_ahead: render (every block as certified; the rejected ones
    are redone in drain), then the bytes, the status and the proofs' verdicts to the host */
-int submit_proven(gss_dev *d, Run &r, Slot &sl, int n_per_blk, int fmt, size_t bb,
-                  hipStream_t st, hipStream_t cp)
+int submit_proven(Run &r, Slot &sl, hipStream_t cp)
 {
+    const hipStream_t st = r.st;
     const SlotDev v = slot_dev(sl);
     const int n_rows = sl.nav_first + sl.n_nav;
     RUN_TRY(hipStreamWaitEvent(st, sl.proved, 0));
@@ -1440,22 +1467,11 @@ int submit_proven(gss_dev *d, Run &r, Slot &sl, int n_per_blk, int fmt, size_t b
        verdicts come back with the bytes and drain redoes the rejected blocks */
     int nf = 0;
     sl.verdicts = 0;
-    const hipError_t q = r.late_verdicts ? hipErrorNotReady : hipEventQuery(sl.proved);
+    const hipError_t q = r.m.late_verdicts ? hipErrorNotReady : hipEventQuery(sl.proved);
     if (q == hipSuccess) {
-        for (int b = 0; b < sl.nb; b++)
-            if (!sl.fast[b])
-                sl.fast[sl.nb + nf++] = b;
-        sl.n_fb = nf;
+        nf = list_exact(sl);
         if (nf > 0) {
-            if (lazy_ck(r))
-                for (int i = 0; i < nf; i++) {
-                    const int b = sl.fast[sl.nb + i];
-                    for (int k = 0; k < sl.nch[b]; k++) {
-                        const size_t e = (size_t)b * GSS_MAXCH + k;
-                        (void)gss_carr_advance_ck(sl.blk[e].carr0, sl.blk[e].carr_step,
-                                                  r.n_per_blk, sl.ck + e * GSS_NCK);
-                    }
-                }
+            fill_lazy_ck(r, sl);
             RUN_H2D(v.ck, sl.ck, sizeof(double) * GSS_MAXCH * GSS_NCK * (size_t)sl.nb, st);
             RUN_H2D(v.fast + sl.nb, sl.fast + sl.nb, sizeof(int32_t) * (size_t)nf, st);
         }
@@ -1464,99 +1480,69 @@ int submit_proven(gss_dev *d, Run &r, Slot &sl, int n_per_blk, int fmt, size_t b
         return gss_fail(GSS_E_HIP, "proof event query: %s", hipGetErrorString(q));
     }
     RUN_TRY(hipMemsetAsync(sl.d_status, 0, sizeof(int32_t), st));
-    int rc = gss_synth_lin_device(d, v.blk, v.nch, sl.nch_max, v.lin, v.fast, v.fast + sl.nb, nf,
-                                  v.ck, r.d_ca, 32, r.d_nav, n_rows > 0 ? n_rows : 1, sl.nb,
-                                  n_per_blk, fmt, sl.d_out, sl.d_status, st);
+    int rc = gss_synth_lin_device(r.dev, v.blk, v.nch, sl.nch_max, v.lin, v.fast, v.fast + sl.nb,
+                                  nf, v.ck, r.d_ca, 32, r.d_nav, n_rows > 0 ? n_rows : 1, sl.nb,
+                                  r.n_per_blk, r.fmt, sl.d_out, sl.d_status, st);
     if (!rc && r.impair)
         rc = impair_blocks(r, sl, 0, sl.nb, st);
     if (rc)
         return rc;
-    RUN_TRY(hipEventRecord(sl.rendered, st));
-    RUN_TRY(hipStreamWaitEvent(cp, sl.rendered, 0));
-    if (sl.tc)
-        RUN_TRY(hipEventRecord(sl.tc, cp));
-    RUN_TRY(hipMemcpyAsync(sl.h_out, slot_bytes(sl), bb * (size_t)sl.nb, hipMemcpyDeviceToHost,
-                           cp));
-    RUN_TRY(hipMemcpyAsync(sl.h_status, sl.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, cp));
-    RUN_TRY(hipMemcpyAsync(sl.fast, v.fast, sizeof(int32_t) * (size_t)sl.nb,
-                           hipMemcpyDeviceToHost, cp));
-    RUN_TRY(hipEventRecord(sl.done, cp));
-    return 0;
+    return slot_download(r, sl, cp, v.fast);
 }
 
-int submit(gss_dev *d, Run &r, Slot &sl, const uint32_t *d_ca, int n_per_blk, int fmt,
-           size_t bb, hipStream_t st, hipStream_t cp)
+int submit(Run &r, Slot &sl, hipStream_t cp)
 {
+    const hipStream_t st = r.st;
     /* the slot's previous D2H must have read d_out before the kernels rewrite it */
     RUN_TRY(hipStreamWaitEvent(st, sl.done, 0));
     if (sl.tq)
         RUN_TRY(hipEventRecord(sl.tq, st));
     if (sl.lin && sl.gpu_proven)
-        return submit_proven(d, r, sl, n_per_blk, fmt, bb, st, cp);
-    const size_t need = slot_dev(sl).need;
-    if (need > sl.d_in_cap) {
-        RUN_TRY(hipStreamSynchronize(st));
-        dev_free(sl.d_in);
-        sl.d_in = nullptr;
-        sl.d_in_cap = 0;
-        RUN_TRY(dev_alloc((void **)&sl.d_in, need));
-        sl.d_in_cap = need;
-    }
+        return submit_proven(r, sl, cp);
+    int rc = slot_in_reserve(sl, st);
+    if (rc)
+        return rc;
     const double tq0 = trace_on() ? tnow() : 0.0;
     const SlotDev v = slot_dev(sl);
-    gss_chan_blk_t *d_blk = v.blk;
-    int32_t *d_nch = v.nch;
-    double *d_ck = v.ck;
-    gss_nav_src_t *d_src = v.src;
-    gss_lin_t *d_lin = v.lin;
-    int32_t *d_fast = v.fast;
-    const size_t s_blk = sizeof(gss_chan_blk_t) * GSS_MAXCH * (size_t)sl.nb;
-    const size_t s_lin = sizeof(gss_lin_t) * GSS_MAXCH * (size_t)sl.nb;
-    RUN_H2D(d_blk, sl.blk, s_blk, st);
-    RUN_H2D(d_nch, sl.nch, sizeof(int32_t) * (size_t)sl.nb, st);
-    RUN_H2D(d_ck, sl.ck, sizeof(double) * GSS_MAXCH * GSS_NCK * (size_t)sl.nb, st);
+    RUN_H2D(v.blk, sl.blk, sizeof(gss_chan_blk_t) * GSS_MAXCH * (size_t)sl.nb, st);
+    RUN_H2D(v.nch, sl.nch, sizeof(int32_t) * (size_t)sl.nb, st);
+    RUN_H2D(v.ck, sl.ck, sizeof(double) * GSS_MAXCH * GSS_NCK * (size_t)sl.nb, st);
     /* the 30 s producer: this slot's new nav rows built on the device (gss_producers.hip); with
        GPU proofs in the run the planner has built them already (proof_ahead) */
     const int n_rows = sl.nav_first + sl.n_nav;
-    int rc = r.gpu_proof ? 0 : nav_reserve(r, (size_t)(n_rows > 0 ? n_rows : 1), st);
+    rc = r.m.gpu_proof ? 0 : nav_reserve(r, (size_t)(n_rows > 0 ? n_rows : 1));
     if (rc)
         return rc;
-    if (r.gpu_proof) {
+    if (r.m.gpu_proof) {
         RUN_TRY(hipStreamWaitEvent(st, sl.navd, 0));
     } else if (sl.n_nav > 0) {
-        RUN_H2D(d_src, sl.nav, sizeof(gss_nav_src_t) * (size_t)sl.n_nav, st);
-        rc = gss_nav_rows_device(d, d_src, sl.nav_first, sl.n_nav, r.d_nav, st);
+        RUN_H2D(v.src, sl.nav, sizeof(gss_nav_src_t) * (size_t)sl.n_nav, st);
+        rc = gss_nav_rows_device(r.dev, v.src, sl.nav_first, sl.n_nav, r.d_nav, st);
         if (rc)
             return rc;
     }
-    const uint32_t *d_nav = r.d_nav;
     const double tq1 = trace_on() ? tnow() : 0.0;
     RUN_TRY(hipMemsetAsync(sl.d_status, 0, sizeof(int32_t), st));
     if (sl.lin) {
-        RUN_H2D(d_lin, sl.lin, s_lin, st);
-        RUN_H2D(d_fast, sl.fast, sizeof(int32_t) * (size_t)(sl.nb + sl.n_fb), st);
+        RUN_H2D(v.lin, sl.lin, sizeof(gss_lin_t) * GSS_MAXCH * (size_t)sl.nb, st);
+        RUN_H2D(v.fast, sl.fast, sizeof(int32_t) * (size_t)(sl.nb + sl.n_fb), st);
         if (sl.tk)
             RUN_TRY(hipEventRecord(sl.tk, st));
-        rc = gss_synth_lin_device(d, d_blk, d_nch, sl.nch_max, d_lin, d_fast, d_fast + sl.nb,
-                                  sl.n_fb, d_ck, d_ca, 32, d_nav, n_rows, sl.nb, n_per_blk,
-                                  fmt, sl.d_out, sl.d_status, st);
+        rc = gss_synth_lin_device(r.dev, v.blk, v.nch, sl.nch_max, v.lin, v.fast, v.fast + sl.nb,
+                                  sl.n_fb, v.ck, r.d_ca, 32, r.d_nav, n_rows, sl.nb, r.n_per_blk,
+                                  r.fmt, sl.d_out, sl.d_status, st);
     } else {
-        rc = gss_synth_device(d, d_blk, d_nch, sl.nch_max, d_ck, d_ca, 32, d_nav, n_rows,
-                              sl.nb, n_per_blk, fmt, sl.d_out, nullptr, sl.d_status, st);
+        rc = gss_synth_device(r.dev, v.blk, v.nch, sl.nch_max, v.ck, r.d_ca, 32, r.d_nav, n_rows,
+                              sl.nb, r.n_per_blk, r.fmt, sl.d_out, nullptr, sl.d_status, st);
     }
     if (!rc && r.impair)
         rc = impair_blocks(r, sl, 0, sl.nb, st);
     if (rc)
         return rc;
     const double tq2 = trace_on() ? tnow() : 0.0;
-    RUN_TRY(hipEventRecord(sl.rendered, st));
-    RUN_TRY(hipStreamWaitEvent(cp, sl.rendered, 0));
-    if (sl.tc)
-        RUN_TRY(hipEventRecord(sl.tc, cp));
-    RUN_TRY(hipMemcpyAsync(sl.h_out, slot_bytes(sl), bb * (size_t)sl.nb, hipMemcpyDeviceToHost,
-                           cp));
-    RUN_TRY(hipMemcpyAsync(sl.h_status, sl.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, cp));
-    RUN_TRY(hipEventRecord(sl.done, cp));
+    rc = slot_download(r, sl, cp, nullptr);
+    if (rc)
+        return rc;
     if (trace_on())
         fprintf(stderr, "trace submit_parts start %.6f h2d %.6f render %.6f out %.6f\n", tq0, tq1, tq2,
                 tnow());
@@ -1567,36 +1553,26 @@ int submit(gss_dev *d, Run &r, Slot &sl, const uint32_t *d_ca, int n_per_blk, in
    again on the exact path alone (their checkpoints from the rows' exact carriers; the fast
    flags zeroed on the device, so that the fast kernel renders nothing), and only their bytes
    copied to the host again; synchronous */
-int redo_rejected(gss_dev *d, Run &r, Slot &sl, const uint32_t *d_ca, int n_rows, int n_per_blk,
-                  int fmt, size_t bb, hipStream_t st)
+int redo_rejected(Run &r, Slot &sl)
 {
-    int nf = 0;
-    for (int b = 0; b < sl.nb; b++)
-        if (!sl.fast[b])
-            sl.fast[sl.nb + nf++] = b;
+    const hipStream_t st = r.st;
+    const size_t bb = r.bb;
+    const int n_rows = sl.nav_first + sl.n_nav;
+    const int nf = list_exact(sl);
     if (nf == 0)
         return 0;
-    sl.n_fb = nf;
-    if (lazy_ck(r))
-        for (int i = 0; i < nf; i++) {
-            const int b = sl.fast[sl.nb + i];
-            for (int k = 0; k < sl.nch[b]; k++) {
-                const size_t e = (size_t)b * GSS_MAXCH + k;
-                (void)gss_carr_advance_ck(sl.blk[e].carr0, sl.blk[e].carr_step, r.n_per_blk,
-                                          sl.ck + e * GSS_NCK);
-            }
-        }
+    fill_lazy_ck(r, sl);
     const SlotDev v = slot_dev(sl);
     RUN_H2D(v.ck, sl.ck, sizeof(double) * GSS_MAXCH * GSS_NCK * (size_t)sl.nb, st);
     RUN_TRY(hipMemsetAsync(v.fast, 0, sizeof(int32_t) * (size_t)sl.nb, st));
     RUN_H2D(v.fast + sl.nb, sl.fast + sl.nb, sizeof(int32_t) * (size_t)nf, st);
     RUN_TRY(hipMemsetAsync(sl.d_status, 0, sizeof(int32_t), st));
-    int rc = gss_synth_lin_device(d, v.blk, v.nch, sl.nch_max, v.lin, v.fast, v.fast + sl.nb, nf,
-                                  v.ck, d_ca, 32, r.d_nav, n_rows, sl.nb, n_per_blk, fmt,
+    int rc = gss_synth_lin_device(r.dev, v.blk, v.nch, sl.nch_max, v.lin, v.fast, v.fast + sl.nb,
+                                  nf, v.ck, r.d_ca, 32, r.d_nav, n_rows, sl.nb, r.n_per_blk, r.fmt,
                                   sl.d_out, sl.d_status, st);
     if (rc)
         return rc;
-    for (int i = 0; i < nf;) {                        /* runs of consecutive rejected blocks */
+    for (int i = 0; i < nf;) {                       /* runs of consecutive rejected blocks */
         const int b0 = sl.fast[sl.nb + i];
         int j = i + 1;
         while (j < nf && sl.fast[sl.nb + j] == b0 + (j - i))
@@ -1616,20 +1592,19 @@ int redo_rejected(gss_dev *d, Run &r, Slot &sl, const uint32_t *d_ca, int n_rows
     return 0;
 }
 
-int drain(gss_dev *d, Run &r, Slot &sl, const uint32_t *d_ca, int n_per_blk, int fmt,
-          size_t bb, hipStream_t st, gss_sink_fn sink, void *user)
+int drain(Run &r, Slot &sl, gss_sink_fn sink, void *user)
 {
     const double t0 = trace_on() ? tnow() : 0.0;
     RUN_TRY(hipEventSynchronize(sl.done));
     const double t1 = trace_on() ? tnow() : 0.0;
     if (sl.lin && sl.gpu_proven && !sl.verdicts && !*sl.h_status) {
-        int rc = redo_rejected(d, r, sl, d_ca, sl.nav_first + sl.n_nav, n_per_blk, fmt, bb, st);
+        int rc = redo_rejected(r, sl);
         if (rc)
             return rc;
     }
     if (*sl.h_status)
         return gss_fail(GSS_E_RANGE, "nav word index ran past dwrd[59]");
-    if (sink(user, sl.h_out, bb * (size_t)sl.nb, sl.first, sl.nb))
+    if (sink(user, sl.h_out, r.bb * (size_t)sl.nb, sl.first, sl.nb))
         return gss_fail(GSS_E_IO, "sink failed at block %lld", (long long)sl.first);
     if (trace_on()) {
         fprintf(stderr, "trace drain first %lld wait %.6f %.6f sink_end %.6f\n",
@@ -1646,22 +1621,12 @@ int drain(gss_dev *d, Run &r, Slot &sl, const uint32_t *d_ca, int n_per_blk, int
                     "copy %.3f\n", (long long)sl.first, a, k, b, c, q);
         }
     }
-    {
-        std::lock_guard<std::mutex> lk(r.mu);
-        sl.state = FREE;
-    }
-    r.cv.notify_all();
+    post(r, sl.state, FREE);
     return 0;
 }
 
 /* GSS_RUN_SPEC_CUS=N (measurement): the walks' stream on N of the device's CUs, spread over
    them (every (ncu / N)-th), and with GSS_RUN_RENDER_REST=1 the render stream on the others */
-int spec_cus()
-{
-    const char *e = getenv("GSS_RUN_SPEC_CUS");
-    return e && *e ? atoi(e) : 0;
-}
-
 hipError_t cu_mask_stream(hipStream_t *st, int n_sel, bool rest)
 {
     int dev = 0, ncu = 0;
@@ -1677,16 +1642,7 @@ hipError_t cu_mask_stream(hipStream_t *st, int n_sel, bool rest)
     return hipExtStreamCreateWithCUMask(st, (uint32_t)m.size(), m.data());
 }
 
-bool make_streams(hipStream_t *cp)
-{
-    for (int k = 0; k < NCOPY; k++)
-        if (stream_get(&cp[k], false) != hipSuccess)
-            return false;
-    return true;
-}
-
-int run_main(gss_dev *d, Run &r, int n_per_blk, int fmt, size_t bb, gss_sink_fn sink,
-             void *user, hipStream_t st, hipStream_t *cp, const uint32_t *d_ca)
+int run_main(Run &r, gss_sink_fn sink, void *user)
 {
     int pending[DEPTH], np = 0, head = 0;              /* submitted, not yet drained (FIFO) */
     for (int i = 0;; i++) {
@@ -1698,18 +1654,18 @@ int run_main(gss_dev *d, Run &r, int n_per_blk, int fmt, size_t bb, gss_sink_fn 
         if (sl.end) {
             int rc = 0;
             for (; np > 0 && rc == 0; np--, head = (head + 1) % DEPTH)
-                rc = drain(d, r, r.slot[pending[head]], d_ca, n_per_blk, fmt, bb, st, sink, user);
+                rc = drain(r, r.slot[pending[head]], sink, user);
             return sl.err ? sl.err : rc;
         }
         if (np == DEPTH) {                             /* oldest slot out to the sink */
-            int rc = drain(d, r, r.slot[pending[head]], d_ca, n_per_blk, fmt, bb, st, sink, user);
+            int rc = drain(r, r.slot[pending[head]], sink, user);
             if (rc)
                 return rc;
             head = (head + 1) % DEPTH;
             np--;
         }
         const double ts0 = trace_on() ? tnow() : 0.0;
-        int rc = submit(d, r, sl, d_ca, n_per_blk, fmt, bb, st, cp[i % NCOPY]);
+        int rc = submit(r, sl, r.cp[i % NCOPY]);
         if (trace_on())
             fprintf(stderr, "trace submit slot %d %.6f %.6f\n", i % NSLOT, ts0, tnow());
         if (rc)
@@ -1717,6 +1673,283 @@ int run_main(gss_dev *d, Run &r, int n_per_blk, int fmt, size_t bb, gss_sink_fn 
         pending[(head + np) % DEPTH] = i % NSLOT;
         np++;
     }
+}
+
+/* Set-up and teardown: each owner's allocation beside its release.  An alloc returns at its
+   first failure; tear_down then releases whatever was made (every release takes nulls).  The
+   order of the allocations and of the releases is the buffer and stream pools' order: the next
+   run of the process finds them as this one left them. */
+
+/* a sequence of HIP calls up to its first failure */
+#define THEN(e, x)                                                                           \
+    do {                                                                                     \
+        if ((e) == hipSuccess)                                                               \
+            (e) = (x);                                                                       \
+    } while (0)
+
+/* The run's streams and its device C/A table, built on the compute stream by the 30 s producer
+   (gss_producers.hip; r.ca is the proofs' copy on the host).  The device nav table (nav_reserve)
+   goes with the C/A table. */
+int run_alloc(Run &r)
+{
+    gss_ca_table(r.ca);
+    hipError_t e = dev_alloc((void **)&r.d_ca, sizeof r.ca);
+    THEN(e, r.m.render_rest ? cu_mask_stream(&r.st, r.m.spec_cus, true) : stream_get(&r.st, false));
+    for (hipStream_t &c : r.cp)
+        THEN(e, stream_get(&c, false));
+    if (trace_on()) {
+        THEN(e, hipEventCreate(&r.t_base));
+        THEN(e, hipEventRecord(r.t_base, r.st));
+    }
+    if (e != hipSuccess)
+        return gss_fail(GSS_E_HIP, "run setup failed");
+    return gss_ca_table_device(r.dev, r.d_ca, r.st);
+}
+
+void run_release_tables(Run &r)
+{
+    dev_free(r.d_ca);
+    dev_free(r.d_nav);
+}
+
+void run_release_streams(Run &r)
+{
+    stream_put(r.st);
+    for (hipStream_t c : r.cp)
+        stream_put(c);
+    if (r.t_base) (void)hipEventDestroy(r.t_base);
+}
+
+/* A slot's buffers and events.  Three more come later and leave with the rest: nav
+   (take_nav_sources), d_in (slot_in_reserve) and anch (spec_alloc). */
+int slot_alloc(const Run &r, Slot &sl)
+{
+    const size_t nb = (size_t)r.batch;
+    const unsigned ev = trace_on() ? hipEventDefault : hipEventDisableTiming;
+    hipError_t e = pin_alloc((void **)&sl.blk, sizeof(gss_chan_blk_t) * GSS_MAXCH * nb);
+    THEN(e, pin_alloc((void **)&sl.nch, sizeof(int32_t) * nb));
+    THEN(e, pin_alloc((void **)&sl.ck, sizeof(double) * GSS_MAXCH * GSS_NCK * nb));
+    THEN(e, pool_get((void **)&sl.h_out, r.bb * nb, true, r.ordinal, &sl.h_out_bytes));
+    THEN(e, pin_alloc((void **)&sl.h_status, sizeof(int32_t)));
+    THEN(e, pool_get((void **)&sl.d_out, r.bb_r * nb, false, r.ordinal, &sl.d_out_bytes));
+    if (r.impair && r.fmt != r.fmt_out)
+        THEN(e, pool_get((void **)&sl.d_imp, r.bb * nb, false, r.ordinal, &sl.d_imp_bytes));
+    THEN(e, dev_alloc((void **)&sl.d_status, sizeof(int32_t)));
+    THEN(e, hipEventCreateWithFlags(&sl.done, ev));
+    THEN(e, hipEventCreateWithFlags(&sl.rendered, ev));
+    if (trace_on()) {
+        THEN(e, hipEventCreate(&sl.tq));
+        THEN(e, hipEventCreate(&sl.tk));
+        THEN(e, hipEventCreate(&sl.tc));
+    }
+    if (e != hipSuccess)
+        return gss_fail(GSS_E_NOMEM, "run buffers (%zu B per slot)", r.bb * nb);
+    if (r.m.use_lin) {
+        THEN(e, pin_alloc((void **)&sl.lin, sizeof(gss_lin_t) * GSS_MAXCH * nb));
+        THEN(e, pin_alloc((void **)&sl.fast, sizeof(int32_t) * 2 * nb));
+        if (e != hipSuccess)
+            return gss_fail(GSS_E_NOMEM, "run lines (%zu B per slot)",
+                            sizeof(gss_lin_t) * GSS_MAXCH * nb);
+    }
+    return 0;
+}
+
+void slot_release(const Run &r, Slot &sl)
+{
+    pin_free(sl.blk); pin_free(sl.nch); pin_free(sl.ck);
+    pin_free(sl.nav); pin_free(sl.h_status);
+    pool_put(sl.h_out, sl.h_out_bytes, true, r.ordinal);
+    pool_put(sl.d_out, sl.d_out_bytes, false, r.ordinal);
+    pool_put(sl.d_imp, sl.d_imp_bytes, false, r.ordinal);
+    pin_free(sl.lin); pin_free(sl.fast); pin_free(sl.anch);
+    dev_free(sl.d_in); dev_free(sl.d_status);
+    if (sl.done) (void)hipEventDestroy(sl.done);
+    if (sl.rendered) (void)hipEventDestroy(sl.rendered);
+    if (sl.tq) (void)hipEventDestroy(sl.tq);
+    if (sl.tk) (void)hipEventDestroy(sl.tk);
+    if (sl.tc) (void)hipEventDestroy(sl.tc);
+}
+
+/* a batch of the chain run ahead: its rows, and the walkers' buffers (records mode: the walks
+   stay on the device and the records come back; else the walks come back) */
+int spec_batch_alloc(const Run &r, Run::SpecBatch &b)
+{
+    const size_t nb = (size_t)r.batch, rows = nb * GSS_MAXCH;
+    b.blk.resize(rows);
+    b.nch.resize(nb);
+    b.chain.resize(rows);
+    hipError_t e = hipEventCreateWithFlags(&b.walked, hipEventDisableTiming);
+    THEN(e, hipEventCreateWithFlags(&b.consumed, hipEventDisableTiming));
+    THEN(e, pin_alloc((void **)&b.h_in, sizeof(gss_spec_in_t) * rows));
+    if (r.m.rec) {
+        THEN(e, dev_alloc((void **)&b.d_in, sizeof(gss_spec_in_t) * rows));
+        THEN(e, dev_alloc((void **)&b.d_spec, sizeof(gss_spec_t) * rows));
+        THEN(e, pin_alloc((void **)&b.h_rec, sizeof(gss_spec_rec_t) * rows));
+    } else {
+        THEN(e, pin_alloc((void **)&b.h_spec, sizeof(gss_spec_t) * rows));
+    }
+    return e == hipSuccess ? 0
+                           : gss_fail(GSS_E_NOMEM, "run carrier-chain buffers (%zu rows)", rows);
+}
+
+void spec_batch_release(Run::SpecBatch &b)
+{
+    pin_free(b.h_in); pin_free(b.h_spec); pin_free(b.h_rec);
+    dev_free(b.d_in); dev_free(b.d_spec);
+    if (b.walked) (void)hipEventDestroy(b.walked);
+    if (b.consumed) (void)hipEventDestroy(b.consumed);
+}
+
+/* the chain run ahead (r.m.spec): the walks' stream, their warm-up scratch, the batches, and the
+   slots' anchors for the proofs' carrier walks */
+int spec_alloc(Run &r)
+{
+    /* high priority: the walks wait for free CUs behind the render kernels otherwise */
+    hipError_t e = r.m.spec_cus > 0 ? cu_mask_stream(&r.spec_st, r.m.spec_cus, false)
+                                    : stream_get(&r.spec_st, true);
+    THEN(e, dev_alloc((void **)&r.spec_warm, WARM_BYTES));
+    if (e != hipSuccess)
+        return gss_fail(GSS_E_HIP, "run carrier-chain stream");
+    for (Run::SpecBatch &b : r.sb) {
+        const int rc = spec_batch_alloc(r, b);
+        if (rc)
+            return rc;
+    }
+    const size_t rows = (size_t)r.batch * GSS_MAXCH;
+    if (r.m.anchors)
+        for (Slot &sl : r.slot)
+            if (pin_alloc((void **)&sl.anch, sizeof(gss_carr_anchor_t) * rows) != hipSuccess)
+                return gss_fail(GSS_E_NOMEM, "run anchors (%zu rows)", rows);
+    return 0;
+}
+
+void spec_release(Run &r)
+{
+    if (r.spec_st) (void)hipStreamSynchronize(r.spec_st);   /* before its batches go */
+    for (Run::SpecBatch &b : r.sb)
+        spec_batch_release(b);
+    dev_free(r.spec_warm);
+    stream_put(r.spec_st);
+}
+
+/* rows ahead (r.m.rows_ahead): the rows thread's batches and the planner's slot carriers; host
+   memory only, released with the Run */
+int rows_alloc(Run &r, const gss_scn_info_t &info)
+{
+    const size_t nb = (size_t)r.batch;
+    /* the nav table's host copy never moves while the prover reads it (take_rows still grows it
+       safely if the bound were passed) */
+    r.nav_rows_h.reserve(nav_rows_bound(r.scn, info) * GSS_NAV_WORDS);
+    for (Run::RowBatch &q : r.rb) {
+        q.blk.resize(nb * GSS_MAXCH);
+        q.nch.resize(nb);
+        q.chain.resize(nb * GSS_MAXCH);
+    }
+    return gss_scn_carrier(r.scn, r.carr);
+}
+
+/* GPU proofs (r.m.gpu_proof), run ahead on the slots' own streams (proof_ahead): those streams
+   and their events, the planner's nav stream, and the device nav table reserved for the whole run
+   (nav_rows_bound; released with the run's tables) */
+int proof_alloc(Run &r, const gss_scn_info_t &info, double t_reserve)
+{
+    if (stream_get(&r.nav_st, false) != hipSuccess)
+        return gss_fail(GSS_E_HIP, "run nav stream");
+    for (Slot &sl : r.slot) {
+        hipError_t e = stream_get(&sl.pst, true);
+        THEN(e, hipEventCreateWithFlags(&sl.navd, hipEventDisableTiming));
+        THEN(e, hipEventCreateWithFlags(&sl.proved, hipEventDisableTiming));
+        if (e != hipSuccess)
+            return gss_fail(GSS_E_HIP, "run proof streams");
+    }
+    const double t_pst = trace_on() ? tnow() : 0.0;
+    const int rc = nav_reserve(r, nav_rows_bound(r.scn, info));
+    if (rc)
+        return rc;
+    /* the C/A table (built on the compute stream, run_alloc) before any proof stream reads it:
+       an event the proof streams wait for (a host wait here held the start-up for the table's
+       first kernel, ~20 ms in a fresh process) */
+    hipError_t e = hipEventCreateWithFlags(&r.ca_ready, hipEventDisableTiming);
+    THEN(e, hipEventRecord(r.ca_ready, r.st));
+    for (Slot &sl : r.slot)
+        THEN(e, hipStreamWaitEvent(sl.pst, r.ca_ready, 0));
+    if (e != hipSuccess)
+        return gss_fail(GSS_E_HIP, "run set-up");
+    if (trace_on())
+        fprintf(stderr, "trace setup_proofs streams %.6f nav_ca %.6f\n", t_pst - t_reserve,
+                tnow() - t_pst);
+    return 0;
+}
+
+void proof_release(Run &r)
+{
+    for (Slot &sl : r.slot) {
+        stream_put(sl.pst);
+        if (sl.navd) (void)hipEventDestroy(sl.navd);
+        if (sl.proved) (void)hipEventDestroy(sl.proved);
+    }
+    stream_put(r.nav_st);
+    if (r.ca_ready) (void)hipEventDestroy(r.ca_ready);
+}
+
+int set_up(Run &r, const gss_scn_info_t &info, double t_enter)
+{
+    int rc = run_alloc(r);
+    for (Slot &sl : r.slot)
+        if (!rc)
+            rc = slot_alloc(r, sl);
+    const double t_slots = trace_on() ? tnow() : 0.0;
+    if (!rc && r.m.spec)
+        rc = spec_alloc(r);
+    if (!rc && r.m.rows_ahead)
+        rc = rows_alloc(r, info);
+    const double t_rows = trace_on() ? tnow() : 0.0;
+    if (!rc)
+        rc = gss_dev_reserve(r.dev, r.batch, r.n_per_blk);
+    const double t_reserve = trace_on() ? tnow() : 0.0;
+    if (trace_on())
+        fprintf(stderr, "trace setup_parts slots %.6f spec_rows %.6f reserve %.6f\n",
+                t_slots - t_enter, t_rows - t_slots, t_reserve - t_rows);
+    if (!rc && r.m.gpu_proof)
+        rc = proof_alloc(r, info, t_reserve);
+    return rc;
+}
+
+/* Every stream that may still touch a slot's memory is synchronised before the slots go, the
+   walks' stream before its batches (spec_release); the run's own streams go back last. */
+void tear_down(Run &r)
+{
+    if (r.st) (void)hipStreamSynchronize(r.st);
+    for (hipStream_t c : r.cp)
+        if (c) (void)hipStreamSynchronize(c);
+    if (r.nav_st) (void)hipStreamSynchronize(r.nav_st);
+    for (Slot &sl : r.slot)                            /* proofs run ahead, not yet rendered */
+        if (sl.pst) (void)hipStreamSynchronize(sl.pst);
+    for (Slot &sl : r.slot)
+        slot_release(r, sl);
+    proof_release(r);
+    run_release_tables(r);
+    spec_release(r);
+    if (trace_on() && r.spec_rows)
+        fprintf(stderr, "trace spec total rows %lld hits %lld\n", (long long)r.spec_rows,
+                (long long)r.spec_hits);
+    run_release_streams(r);
+}
+
+/* the walks' first launch costs ~1 ms (the kernel's first use): here, on one zero row, while
+   the planner produces its first rows, instead of inside its first batch */
+void warm_walks(Run &r)
+{
+    uint8_t *w = (uint8_t *)r.spec_warm;
+    (void)hipMemsetAsync(r.spec_warm, 0, WARM_BYTES, r.spec_st);
+    (void)gss_spec_device(r.dev, (gss_spec_in_t *)w, 1, r.n_per_blk,
+                          (gss_spec_t *)(w + 2 * WARM_IN), r.spec_st);
+    if (!r.m.rec)
+        return;
+    (void)hipMemsetAsync(r.spec_warm, 0, WARM_BYTES, r.spec_st);
+    (void)gss_spec_records_device(r.dev, (gss_spec_in_t *)w, 1, r.n_per_blk,
+                                  (gss_spec_in_t *)(w + WARM_IN), (gss_spec_t *)(w + 2 * WARM_IN),
+                                  (gss_spec_rec_t *)(w + 2 * WARM_IN + WARM_SPEC), r.spec_st);
 }
 
 }  // namespace
@@ -1731,6 +1964,7 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
                           int batch, int threads, gss_sink_fn sink, void *user,
                           const gss_run_opts_t *opts)
 {
+    /* validate */
     if (!d || !s || !sink || first_block < 0)
         return gss_fail(GSS_E_ARG, "invalid run arguments");
     const double t_enter = trace_on() ? tnow() : 0.0;
@@ -1749,321 +1983,70 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
     if (imp && !gss_impair_device)
         return gss_fail(GSS_E_STATE, "additive noise requested, but this build has no "
                                      "impairment launch (gss_impair_device)");
-    const int fmt = imp ? GSS_FMT_SC16 : info.data_format;
     const size_t bb_r = imp ? (size_t)info.n_per_blk * 4 : bb;
-    Run r;
+    if (batch <= 0)
+        batch = 100;
+    if ((size_t)batch * bb_r > SLOT_OUT_MAX)           /* the slots' pinned output buffers */
+        batch = (int)(SLOT_OUT_MAX / bb_r) > 0 ? (int)(SLOT_OUT_MAX / bb_r) : 1;
+    /* the handle may have produced blocks already (an earlier run or seek): the run continues
+       from there; blocks before first_block are planned (the carrier chain) and dropped */
+    if (first_block < info.next_block)
+        return gss_fail(GSS_E_STATE, "run from block %lld, but the scenario is at block %lld",
+                        (long long)first_block, (long long)info.next_block);
+
+    /* the modes, then the run's context */
+    Run r(run_modes_resolve(run_env_read(), opts && opts->carr_in, opts && opts->carr_predict,
+                            info.carrier_int != 0, batch));
     r.scn = s;
+    r.dev = d;
     r.opts = opts;
     r.impair = imp;
+    r.fmt = imp ? GSS_FMT_SC16 : info.data_format;
     r.fmt_out = info.data_format;
-    r.dev = d;
+    r.bb = bb;
+    r.bb_r = bb_r;
     r.carrier_int = info.carrier_int;
     r.threads = threads > 0 ? threads : 1;
     r.n_per_blk = info.n_per_blk;
-    {
-        const char *path = getenv("GSS_PATH");        /* "walk": the exact path for every block */
-        r.use_lin = !(path && strcmp(path, "walk") == 0);
-        const char *fe = getenv("GSS_RUN_FORCE_EXACT");
-        r.force_exact = fe && *fe ? atoi(fe) : 0;
-        const char *lv = getenv("GSS_RUN_LATE_VERDICTS");
-        r.late_verdicts = lv && *lv == '1';
-        const char *up = getenv("GSS_RUN_UPLOAD");
-        r.upload_dev = !(up && strcmp(up, "dma") == 0);
-    }
-    r.batch = batch > 0 ? batch : 100;
-    if ((size_t)r.batch * bb_r > SLOT_OUT_MAX)
-        r.batch = (int)(SLOT_OUT_MAX / bb_r) > 0 ? (int)(SLOT_OUT_MAX / bb_r) : 1;
+    r.batch = batch;
     r.first = first_block;
     r.last = n_blocks < 0 ? INT64_MAX : first_block + n_blocks;
-    /* the handle may have produced blocks already (an earlier run or seek): the run continues
-       from there; blocks before first_block are planned (the carrier chain) and dropped */
     r.start = info.next_block;
-    if (first_block < r.start)
-        return gss_fail(GSS_E_STATE, "run from block %lld, but the scenario is at block %lld",
-                        (long long)first_block, (long long)r.start);
+    RUN_TRY(hipGetDevice(&r.ordinal));
 
-    int ordinal = 0;
-    RUN_TRY(hipGetDevice(&ordinal));
-    hipStream_t st = nullptr, cp[NCOPY] = {};
-    uint32_t *d_ca = nullptr;
-    int err = 0;
-    auto cleanup = [&]() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (hipStream_t c : cp)
-            if (c) (void)hipStreamSynchronize(c);
-        if (r.nav_st) (void)hipStreamSynchronize(r.nav_st);
-        for (Slot &sl : r.slot)                        /* proofs run ahead, not yet rendered */
-            if (sl.pst) (void)hipStreamSynchronize(sl.pst);
-        for (Slot &sl : r.slot) {
-            pin_free(sl.blk); pin_free(sl.nch); pin_free(sl.ck);
-            pin_free(sl.nav); pin_free(sl.h_status);
-            pool_put(sl.h_out, sl.h_out_bytes, true, ordinal);
-            pool_put(sl.d_out, sl.d_out_bytes, false, ordinal);
-            pool_put(sl.d_imp, sl.d_imp_bytes, false, ordinal);
-            pin_free(sl.lin); pin_free(sl.fast); pin_free(sl.anch);
-            dev_free(sl.d_in); dev_free(sl.d_status);
-            if (sl.done) (void)hipEventDestroy(sl.done);
-            if (sl.rendered) (void)hipEventDestroy(sl.rendered);
-            if (sl.tq) (void)hipEventDestroy(sl.tq);
-            if (sl.tk) (void)hipEventDestroy(sl.tk);
-            if (sl.tc) (void)hipEventDestroy(sl.tc);
-        }
-        for (Slot &sl : r.slot) {
-            stream_put(sl.pst);
-            if (sl.navd) (void)hipEventDestroy(sl.navd);
-            if (sl.proved) (void)hipEventDestroy(sl.proved);
-        }
-        stream_put(r.nav_st);
-        dev_free(d_ca);
-        dev_free(r.d_nav);
-        if (r.spec_st) (void)hipStreamSynchronize(r.spec_st);
-        for (Run::SpecBatch &b : r.sb) {
-            pin_free(b.h_in); pin_free(b.h_spec); pin_free(b.h_rec);
-            dev_free(b.d_in); dev_free(b.d_spec);
-            if (b.walked) (void)hipEventDestroy(b.walked);
-            if (b.consumed) (void)hipEventDestroy(b.consumed);
-        }
-        dev_free(r.spec_warm);
-        stream_put(r.spec_st);
-        if (trace_on() && r.spec_rows)
-            fprintf(stderr, "trace spec total rows %lld hits %lld\n", (long long)r.spec_rows,
-                    (long long)r.spec_hits);
-        stream_put(st);
-        for (hipStream_t c : cp)
-            stream_put(c);
-        if (r.t_base) (void)hipEventDestroy(r.t_base);
-        if (r.ca_ready) (void)hipEventDestroy(r.ca_ready);
-    };
-    /* buffers */
-    {
-        gss_ca_table(r.ca);                            /* the proofs' copy, on the host */
-        if (dev_alloc((void **)&d_ca, sizeof r.ca) != hipSuccess ||
-            (spec_cus() > 0 && getenv("GSS_RUN_RENDER_REST")
-                 ? cu_mask_stream(&st, spec_cus(), true)
-                 : stream_get(&st, false)) != hipSuccess ||
-            !make_streams(cp) ||
-            (trace_on() && (hipEventCreate(&r.t_base) != hipSuccess ||
-                            hipEventRecord(r.t_base, st) != hipSuccess)))
-            err = gss_fail(GSS_E_HIP, "run setup failed");
-        /* the kernels' copy built on the device by the 30 s producer (gss_producers.hip) */
-        if (!err)
-            err = gss_ca_table_device(d, d_ca, st);
-        const size_t nb = (size_t)r.batch;
-        for (Slot &sl : r.slot) {
-            if (err) break;
-            if (pin_alloc((void **)&sl.blk, sizeof(gss_chan_blk_t) * GSS_MAXCH * nb) != hipSuccess ||
-                pin_alloc((void **)&sl.nch, sizeof(int32_t) * nb) !=
-                    hipSuccess ||
-                pin_alloc((void **)&sl.ck, sizeof(double) * GSS_MAXCH * GSS_NCK * nb) != hipSuccess ||
-                pool_get((void **)&sl.h_out, bb * nb, true, ordinal, &sl.h_out_bytes) !=
-                    hipSuccess ||
-                pin_alloc((void **)&sl.h_status, sizeof(int32_t)) !=
-                    hipSuccess ||
-                pool_get((void **)&sl.d_out, bb_r * nb, false, ordinal, &sl.d_out_bytes) !=
-                    hipSuccess ||
-                (imp && fmt != r.fmt_out &&
-                 pool_get((void **)&sl.d_imp, bb * nb, false, ordinal, &sl.d_imp_bytes) !=
-                     hipSuccess) ||
-                dev_alloc((void **)&sl.d_status, sizeof(int32_t)) != hipSuccess ||
-                hipEventCreateWithFlags(&sl.done, trace_on() ? hipEventDefault
-                                                             : hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&sl.rendered, trace_on() ? hipEventDefault
-                                                                 : hipEventDisableTiming) !=
-                    hipSuccess ||
-                (trace_on() && (hipEventCreate(&sl.tq) != hipSuccess ||
-                                hipEventCreate(&sl.tk) != hipSuccess ||
-                                hipEventCreate(&sl.tc) != hipSuccess)))
-                err = gss_fail(GSS_E_NOMEM, "run buffers (%zu B per slot)", bb * nb);
-            if (!err && r.use_lin &&
-                (pin_alloc((void **)&sl.lin, sizeof(gss_lin_t) * GSS_MAXCH * nb) != hipSuccess ||
-                 pin_alloc((void **)&sl.fast, sizeof(int32_t) * 2 * nb) != hipSuccess))
-                err = gss_fail(GSS_E_NOMEM, "run lines (%zu B per slot)",
-                               sizeof(gss_lin_t) * GSS_MAXCH * nb);
-        }
-        const double t_slots = trace_on() ? tnow() : 0.0;
-        /* the chain run ahead: fast path, float carrier (per batch, or over the up-front range
-           of a hand-off) */
-        {
-            const char *e = getenv("GSS_RUN_SPEC");
-            r.spec = lazy_ck(r) && !(e && e[0] == '0');
-            const char *er = getenv("GSS_RUN_REC");
-            r.rec = r.spec && !(opts && opts->carr_in && !opts->carr_predict) &&
-                    !(er && er[0] == '0');
-            const char *ed = getenv("GSS_RUN_DEV_ANCHORS");
-            r.dev_anch = ed && ed[0] == '1';
-        }
-        if (!err && r.spec) {
-            const size_t rows = nb * GSS_MAXCH;
-            r.dev = d;
-            /* high priority: the walks wait for free CUs behind the render kernels otherwise */
-            if ((spec_cus() > 0
-                     ? cu_mask_stream(&r.spec_st, spec_cus(), false)
-                     : stream_get(&r.spec_st, true)) !=
-                    hipSuccess ||
-                dev_alloc((void **)&r.spec_warm, WARM_BYTES) != hipSuccess)
-                err = gss_fail(GSS_E_HIP, "run carrier-chain stream");
-            for (Run::SpecBatch &b : r.sb) {
-                if (err) break;
-                b.blk.resize(rows);
-                b.nch.resize(nb);
-                b.chain.resize(rows);
-                if (hipEventCreateWithFlags(&b.walked, hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&b.consumed, hipEventDisableTiming) != hipSuccess ||
-                    pin_alloc((void **)&b.h_in, sizeof(gss_spec_in_t) * rows) != hipSuccess ||
-                    (r.rec ? dev_alloc((void **)&b.d_in, sizeof(gss_spec_in_t) * rows) !=
-                                     hipSuccess ||
-                                 dev_alloc((void **)&b.d_spec, sizeof(gss_spec_t) * rows) !=
-                                     hipSuccess ||
-                                 pin_alloc((void **)&b.h_rec, sizeof(gss_spec_rec_t) * rows) != hipSuccess
-                           : pin_alloc((void **)&b.h_spec, sizeof(gss_spec_t) * rows) != hipSuccess))
-                    err = gss_fail(GSS_E_NOMEM, "run carrier-chain buffers (%zu rows)", rows);
-            }
-            /* the chain's anchors for the proofs' carrier walks (GSS_RUN_ANCHORS=0: none) */
-            const char *ea = getenv("GSS_RUN_ANCHORS");
-            if (r.use_lin && !(opts && opts->carr_in) && !(ea && ea[0] == '0'))
-                for (Slot &sl : r.slot) {
-                    if (err) break;
-                    if (pin_alloc((void **)&sl.anch, sizeof(gss_carr_anchor_t) * rows) != hipSuccess)
-                        err = gss_fail(GSS_E_NOMEM, "run anchors (%zu rows)", rows);
-                }
-        }
-        /* the rows and prover threads where the planner is the limit: slots of >= 1024 blocks
-           (-b 1 at 2.6 MS/s: 2,048).  The D2H-bound formats gain nothing from them, and inside
-           bench.py's process the extra threads cost the -b 16 leg a third of its download rate
-           (profiles/round3/e2e_planner/bench_*_r3af.log); GSS_RUN_ROWS_AHEAD=1 / 0 forces */
-        {
-            const char *e = getenv("GSS_RUN_ROWS_AHEAD");
-            const bool want = e && *e ? e[0] != '0' : r.batch >= 1024;
-            r.rows_ahead = r.spec && !(opts && opts->carr_in) && want;
-        }
-        {
-            /* GSS_RUN_PROOF=gpu: the proofs on the GPU, run ahead by the planner (proof_ahead);
-               host: on the host threads; split: every other slot on the GPU.  The default (auto)
-               proves on the GPU only the planner-bound runs (rows ahead: slots of >= 1024
-               blocks, the -b 1 runs) with the walks' records (no walks on the host): there the
-               host's CPUs are the limit and the proofs take them off it (configs[4] e2e 0.85-0.86
-               against 0.80-0.82 of the D2H ceiling, profiles/round5/e2e/b_*_r5q).  Elsewhere the
-               two are even since the proof kernel spreads a small slot's channels over waves
-               (configs[3]: 0.695-0.702 s against 0.695-0.705, the headline and configs[2] within
-               noise; profiles/round5/e2e/r6e, e2e_modes_r6i.log), and host proofs keep the
-               GPU's queues to the render and the copies */
-            const char *e = getenv("GSS_RUN_PROOF");
-            const int gpu_auto = r.rows_ahead && r.rec ? 1 : 0;
-            r.proof_mode = !r.use_lin ? 0 : !e || !*e || strcmp(e, "auto") == 0 ? gpu_auto :
-                           strcmp(e, "gpu") == 0 ? 1 : strcmp(e, "split") == 0 ? 2 : 0;
-            r.gpu_proof = r.proof_mode != 0;
-        }
-        r.prover = r.rows_ahead && r.use_lin && r.proof_mode != 1;
-        {
-            const char *e = getenv("GSS_RUN_PROVER");
-            if (e && e[0] == '0')
-                r.prover = 0;
-        }
-        if (!err && r.rows_ahead) {
-            /* the nav table's host copy never moves while the prover reads it (take_rows
-               still grows it safely if the bound were passed) */
-            r.nav_rows_h.reserve(nav_rows_bound(s, info) * GSS_NAV_WORDS);
-            for (Run::RowBatch &q : r.rb) {
-                q.blk.resize(nb * GSS_MAXCH);
-                q.nch.resize(nb);
-                q.chain.resize(nb * GSS_MAXCH);
-            }
-            err = gss_scn_carrier(s, r.carr);
-        }
-        const double t_rows = trace_on() ? tnow() : 0.0;
-        if (!err)
-            err = gss_dev_reserve(d, r.batch, info.n_per_blk);
-        const double t_reserve = trace_on() ? tnow() : 0.0;
-        if (trace_on())
-            fprintf(stderr, "trace setup_parts slots %.6f spec_rows %.6f reserve %.6f\n",
-                    t_slots - t_enter, t_rows - t_slots, t_reserve - t_rows);
-        if (!err && r.gpu_proof) {
-            /* proofs run ahead on the slots' own streams (proof_ahead); the device nav table
-               reserved for the whole run (nav_rows_bound) */
-            r.dev = d;
-            r.d_ca = d_ca;
-            if (stream_get(&r.nav_st, false) != hipSuccess)
-                err = gss_fail(GSS_E_HIP, "run nav stream");
-            for (Slot &sl : r.slot) {
-                if (err) break;
-                if (stream_get(&sl.pst, true) != hipSuccess ||
-                    hipEventCreateWithFlags(&sl.navd, hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&sl.proved, hipEventDisableTiming) != hipSuccess)
-                    err = gss_fail(GSS_E_HIP, "run proof streams");
-            }
-            const double t_pst = trace_on() ? tnow() : 0.0;
-            if (!err)
-                err = nav_reserve(r, nav_rows_bound(s, info), st);
-            /* the C/A table (built on st above) before any proof stream reads it: an event the
-               proof streams wait for (a host wait here held the start-up for the table's first
-               kernel, ~20 ms in a fresh process) */
-            if (!err && (hipEventCreateWithFlags(&r.ca_ready, hipEventDisableTiming) != hipSuccess ||
-                         hipEventRecord(r.ca_ready, st) != hipSuccess))
-                err = gss_fail(GSS_E_HIP, "run set-up");
-            for (Slot &sl : r.slot)
-                if (!err && hipStreamWaitEvent(sl.pst, r.ca_ready, 0) != hipSuccess)
-                    err = gss_fail(GSS_E_HIP, "run set-up");
-            if (trace_on())
-                fprintf(stderr, "trace setup_proofs streams %.6f nav_ca %.6f\n", t_pst - t_reserve,
-                        tnow() - t_pst);
-        }
-    }
+    int err = set_up(r, info, t_enter);
     if (err) {
-        cleanup();
+        tear_down(r);
         return err;
     }
     if (trace_on())
         fprintf(stderr, "trace setup enter %.6f ready %.6f\n", t_enter, tnow());
+
+    /* the threads; the walk kernels warmed while the planner produces its first rows */
+    const int ordinal = r.ordinal;
     std::thread th([&r, ordinal] {
         (void)hipSetDevice(ordinal);                   /* pinned reallocations */
         planner(&r);
     });
     std::thread th_rows, th_prove;
-    if (r.rows_ahead)
+    if (r.m.rows_ahead)
         th_rows = std::thread(rows_thread, &r);
-    if (r.prover)
+    if (r.m.prover)
         th_prove = std::thread(prover, &r);
-    if (r.spec) {
-        /* the walks' first launch costs ~1 ms (the kernel's first use): here, on one zero row,
-           while the planner produces its first rows, instead of inside its first batch */
-        uint8_t *w = (uint8_t *)r.spec_warm;
-        (void)hipMemsetAsync(r.spec_warm, 0, WARM_BYTES, r.spec_st);
-        (void)gss_spec_device(d, (gss_spec_in_t *)w, 1, info.n_per_blk,
-                              (gss_spec_t *)(w + 2 * WARM_IN), r.spec_st);
-        if (r.rec) {
-            (void)hipMemsetAsync(r.spec_warm, 0, WARM_BYTES, r.spec_st);
-            (void)gss_spec_records_device(d, (gss_spec_in_t *)w, 1, info.n_per_blk,
-                                          (gss_spec_in_t *)(w + WARM_IN),
-                                          (gss_spec_t *)(w + 2 * WARM_IN),
-                                          (gss_spec_rec_t *)(w + 2 * WARM_IN + WARM_SPEC),
-                                          r.spec_st);
-        }
-    }
-    err = run_main(d, r, info.n_per_blk, fmt, bb, sink, user, st, cp, d_ca);
-    {
-        std::lock_guard<std::mutex> lk(r.mu);
-        r.abort = 1;
-    }
-    r.cv.notify_all();
+    if (r.m.spec)
+        warm_walks(r);
+
+    err = run_main(r, sink, user);
+
+    post(r, r.abort, 1);
     th.join();
     if (th_rows.joinable())
         th_rows.join();
     if (th_prove.joinable())
         th_prove.join();
-    if (r.rows_ahead && !err)                          /* the scenario's carriers: run's end */
+    if (r.m.rows_ahead && !err)                        /* the scenario's carriers: run's end */
         err = gss_scn_set_carrier(s, r.carr);
-    cleanup();
+    tear_down(r);
     return err;
 }
 
-/* Threads besides the planner and main ones (round 3):
- *   rows thread      (chain ahead, no hand-off, slots of >= 1024 blocks unless GSS_RUN_ROWS_AHEAD
- *                    says otherwise) owns the scenario during the run: next_ask's
- *                    batches (gss_scn_next_deferred) with the nav rows and sources new with each,
- *                    a batch ahead of the planner, on its own worker pool; the planner then keeps
- *                    the slot carriers and host copies of the nav table (GSS_RUN_ROWS_AHEAD=0:
- *                    rows on the planner thread; GSS_RUN_ROWS_POOL=0: the planner's pool)
- *   prover thread    (rows ahead, fast path) the slots' proofs in slot order on its own worker
- *                    pool: the planner hands a slot over PROVING, the prover marks it PLANNED
- *                    for the main thread (GSS_RUN_PROVER=0: proofs on the planner thread)
- */

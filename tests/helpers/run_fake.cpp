@@ -11,6 +11,7 @@
  *   GSS_RUN_ROWS_AHEAD=1 / 0 with GSS_RUN_PROVER=0 / 1, GSS_RUN_PROOF=gpu / split,
  *   GSS_RUN_FORCE_EXACT (blocks on the exact path, lazy checkpoints), GSS_RUN_UPLOAD=dma,
  *   GSS_RUN_REC=0 (the walks back instead of records; the chain's anchors for the proofs),
+ *   GSS_PATH=walk (no proofs: gss_synth_device renders every block from its checkpoints),
  *   a range from a mid-run block, two runs on one handle, the carrier hand-off of gss_run_ex
  *   (two ranks in sequence), and a sink that stops the run.
  * Test infrastructure only (no GPU, nothing of it ships).
@@ -129,7 +130,7 @@ struct Mode {
 static const char *ENV_KEYS[] = {"GSS_RUN_SPEC", "GSS_RUN_ROWS_AHEAD", "GSS_RUN_PROVER",
                                  "GSS_RUN_PROOF", "GSS_RUN_FORCE_EXACT", "GSS_RUN_UPLOAD",
                                  "GSS_RUN_ROWS_POOL", "GSS_RUN_REC", "GSS_RUN_ANCHORS",
-                                 "GSS_RUN_DEV_ANCHORS", "GSS_RUN_LATE_VERDICTS"};
+                                 "GSS_RUN_DEV_ANCHORS", "GSS_RUN_LATE_VERDICTS", "GSS_PATH"};
 
 static void set_env(const Mode &m)
 {
@@ -250,6 +251,7 @@ int main(int argc, char **argv)
         {"walks back, anchors, rows ahead, device proofs",
          {{"GSS_RUN_REC", "0"}, {"GSS_RUN_ROWS_AHEAD", "1"}, {"GSS_RUN_PROOF", "gpu"}}},
         {"walks back, no anchors", {{"GSS_RUN_REC", "0"}, {"GSS_RUN_ANCHORS", "0"}}},
+        {"exact path for every block (GSS_PATH=walk)", {{"GSS_PATH", "walk"}}},
     };
     /* RUN_FAKE_QUICK=1 (the CPU suite's sanitizer test): every third mode, the whole-run and
        the two runs on one handle kept; the full list is tools/sanitize.sh's default */

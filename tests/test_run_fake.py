@@ -1,9 +1,10 @@
-"""gss_run (csrc/hip/gss_run.hip, unchanged) on the CPU fake of the HIP runtime.
+"""gss_run (csrc/hip/gss_run.hip and its gss_run_modes.h, as shipped) on the CPU fake of the HIP
+runtime.
 
 tests/helpers/fake_hip stands in for the HIP calls gss_run makes (streams drained by worker
 threads, events as generation counters), tests/helpers/fake_dev.cpp for its device functions
 (renders write a fingerprint of each block's rows and nav words), and run_fake.cpp drives
-every mode of the run (host / gpu / split proofs, two runs on one handle, the two-rank
+every mode of the run (host / gpu / split proofs, GSS_PATH=walk, two runs on one handle, the two-rank
 baton hand-off, a sink that stops) checking every byte the sink receives.  tools/sanitize.sh
 runs the same program under TSan and ASan+UBSan; this is the plain build, so the CPU suite
 catches an orchestration regression without a GPU.

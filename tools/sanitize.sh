@@ -1,8 +1,9 @@
 #!/bin/bash
 # The host side under the sanitizers (CPU only), once with -fsanitize=thread and
 # once with -fsanitize=address,undefined; any sanitizer report, row or byte mismatch fails.
-#  * gss_run itself (gps-sdr-sim_amd/csrc/hip/gss_run.hip, unchanged: its planner, rows and
-#    prover threads, slot state machine, buffer pool, uploads, streams and events) built against
+#  * gss_run itself (gps-sdr-sim_amd/csrc/hip/gss_run.hip with its gss_run_modes.h, as shipped: its
+#    planner, rows and prover threads, slot state machine, buffer pool, uploads, streams and
+#    events) built against
 #    the CPU stand-in of the HIP runtime (tests/helpers/fake_hip) and the CPU fakes of its device
 #    functions (tests/helpers/fake_dev.cpp), driven through every mode of the run by
 #    tests/helpers/run_fake.cpp, which checks every byte the sink gets against independently
