@@ -2,7 +2,9 @@
  * gss_lin.h — the fast path's render arithmetic, restated once for the three places that must
  * agree on it bit for bit: the GPU kernel (gss_lin_kernel, csrc/hip/gss_synth.hip), the host
  * proof that certifies blocks for it (csrc/host/linearize.c) and the CPU checker of the tests
- * (tests/helpers/lin_check.c).
+ * (tests/helpers/lin_check.c).  The rows a wave of the kernel starts a segment from (the lines
+ * evaluated at the segment start: gss_lin_row_at, gss_lin_chan_of, below) are stated here too,
+ * built by the kernel in its set-up and checked on the CPU by tests/helpers/lin_rows.c.
  *
  * A block's channel is described by two 64-bit integer lines (gss_lin_t): the carrier
  * X(p) = x0 + p*xs mod 2^64 [2^-64 cycle] and the code Z(p) = z0 + p*zs [2^-50 chip, unwrapped]
@@ -131,6 +133,103 @@ GSS_LIN_FN uint64_t gss_lin_lane(uint64_t xs, uint64_t zs, uint32_t l)
     const uint32_t lx = (uint32_t)(((uint64_t)l * xs + (1ull << 31)) >> 32);
     const uint32_t lz = (uint32_t)(((uint64_t)l * zs) >> GSS_LIN_CSH);
     return ((uint64_t)lx << 32) | lz;
+}
+
+/* ---- the segment rows: what a wave of gss_lin_kernel starts its GSS_LIN_SEG samples from ------
+   Per (channel, wave segment) the lines are evaluated once at the segment start n0 (a multiple of
+   GSS_LIN_SEG), so that the chunk loop needs no 128-bit arithmetic and no schedule search; per
+   channel the step constants.  gss_lin_kernel builds them in its set-up, one lane per row. */
+typedef struct {
+    uint64_t x;                  /* X(n0) + gss_lin_xa(xs): the first chunk's carrier anchor base */
+    uint64_t z;                  /* ((E0 << 50) | fraction) + gss_lin_za(zs): the first chunk's
+                                    code anchor base, E0 = gss_lin_e0(chip at the segment start) */
+    int32_t g01;                 /* signed gain at the start (low 16) and after pos1 (high 16)   */
+    int32_t pos1;                /* sample of the first gain change in the segment, or INT32_MAX */
+    uint32_t npatch;             /* patched samples of the channel inside the segment            */
+    uint32_t pad;
+} gss_lin_row;
+typedef struct {
+    uint64_t xs, zs;             /* the lines' per-sample steps                                  */
+    uint64_t d;                  /* the 64-sample step dX : dC of P (gss_lin_dx : gss_lin_dz)    */
+    uint32_t dq;                 /* window offset advance per step, 1/16 chip, rounded down      */
+    uint32_t tab;                /* the channel's C/A table row                                  */
+} gss_lin_chan;
+
+GSS_LIN_FN uint64_t gss_lin_mulhi(uint64_t a, uint64_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(a, b);
+#else
+    return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+
+/* the carrier anchor base of the segment that starts at n0 */
+GSS_LIN_FN uint64_t gss_lin_row_x(uint64_t x0, uint64_t xs, uint64_t n0)
+{
+    return x0 + n0 * xs + gss_lin_xa(xs);
+}
+/* the code anchor base: Z(n0) = z0 + n0 zs in 128 bits (hi : lo), its chips reduced by
+   gss_lin_e0, the fraction kept */
+GSS_LIN_FN uint64_t gss_lin_row_z(uint64_t z0, uint64_t zs, uint64_t n0)
+{
+    const uint64_t lo = z0 + n0 * zs;
+    const uint64_t hi = gss_lin_mulhi(n0, zs) + (lo < z0 ? 1u : 0u);
+    const uint32_t e0 = gss_lin_e0((hi << 14) | (lo >> 50));
+    return (((uint64_t)e0 << 50) | (lo & ((1ull << 50) - 1))) + gss_lin_za(zs);
+}
+/* the gain pair and pos1 from the schedule gpos[i] <= p < gpos[i+1] -> gval[i] (ngc entries,
+   gpos[0] = 0, unused = INT32_MAX); writes g01 and pos1 of *r */
+GSS_LIN_FN void gss_lin_row_gain(gss_lin_row *r, const int32_t *gpos, const int32_t *gval, int ngc,
+                                 int32_t n0)
+{
+    /* gpos ascends, so the entries at or before n0 are a prefix (the last of them holds the gain
+       at n0) and the first entry after n0 is the next change.  Every entry is read, with no
+       early exit: the kernel's loads are then independent of each other (one round trip) */
+    int32_t g0 = gval[0], gn = 0, pn = INT32_MAX;
+    for (int i = 1; i < ngc; i++) {
+        const int32_t p = gpos[i], v = gval[i];
+        g0 = p <= n0 ? v : g0;
+    }
+    for (int i = ngc - 1; i >= 1; i--) {
+        const int32_t p = gpos[i], v = gval[i];
+        gn = p > n0 ? v : gn;
+        pn = p > n0 ? p : pn;
+    }
+    const int more = pn < n0 + GSS_LIN_SEG;            /* (unused entries: INT32_MAX, never) */
+    const int32_t g1 = more ? gn : g0;
+    r->g01 = (int32_t)(((uint32_t)g0 & 0xFFFFu) | ((uint32_t)g1 << 16));
+    r->pos1 = more ? pn : INT32_MAX;
+}
+/* the patched samples (ppos, np entries) inside the segment */
+GSS_LIN_FN uint32_t gss_lin_row_npatch(const int32_t *ppos, int np, int32_t n0)
+{
+    uint32_t n = 0;
+    for (int j = 0; j < np; j++)
+        n += ppos[j] >= n0 && ppos[j] < n0 + GSS_LIN_SEG;
+    return n;
+}
+GSS_LIN_FN gss_lin_row gss_lin_row_at(uint64_t x0, uint64_t xs, uint64_t z0, uint64_t zs,
+                                      const int32_t *gpos, const int32_t *gval, int ngc,
+                                      const int32_t *ppos, int np, int32_t n0)
+{
+    gss_lin_row r;
+    r.x = gss_lin_row_x(x0, xs, (uint64_t)n0);
+    r.z = gss_lin_row_z(z0, zs, (uint64_t)n0);
+    gss_lin_row_gain(&r, gpos, gval, ngc, n0);
+    r.npatch = gss_lin_row_npatch(ppos, np, n0);
+    r.pad = 0;
+    return r;
+}
+GSS_LIN_FN gss_lin_chan gss_lin_chan_of(uint64_t xs, uint64_t zs, uint32_t ca_tbl)
+{
+    gss_lin_chan c;
+    c.xs = xs;
+    c.zs = zs;
+    c.d = ((uint64_t)gss_lin_dx(xs) << 32) | gss_lin_dz(zs);
+    c.dq = (uint32_t)((zs * 64u) >> 46);
+    c.tab = ca_tbl;
+    return c;
 }
 
 /* the kernel's LUT cell and chip at block sample p (128-bit code line; the proof's, on the host

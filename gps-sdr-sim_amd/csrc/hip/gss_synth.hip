@@ -577,70 +577,12 @@ struct alignas(16) lin_ct {
    by the hardware and cost the round-4 LDS-window build 3x) */
 static_assert(offsetof(lin_ct, A) % 8 == 0, "lin_ct.A: 8-byte reads");
 
-/* per (block, channel): the render constants of gss_lin.h (written by gss_linseg_kernel) */
-struct lin_chan {
-    uint64_t xs, zs;             /* the lines' per-sample steps                                 */
-    uint64_t d;                  /* the 64-sample step dX : dC of P (gss_lin_dx : gss_lin_dz)    */
-    uint32_t dq;                 /* window offset advance per step, 1/16 chip, rounded down      */
-    uint32_t tab;                /* the channel's C/A table row                                  */
-};
-/* per (block, channel, wave segment of 64*LIN_STEPS samples): the lines at the segment start,
-   so that the render kernel needs no 128-bit arithmetic and no schedule search */
-struct lin_seg {
-    uint64_t x;                  /* X(n0) + gss_lin_xa(xs): the first chunk's carrier anchor base */
-    uint64_t z;                  /* ((E0 << 50) | fraction) + gss_lin_za(zs): the first chunk's
-                                    code anchor base, E0 = gss_lin_e0(chip at the segment start) */
-    int32_t g01;                 /* signed gain at the start (low 16) and after pos1 (high 16)   */
-    int32_t pos1;                /* sample of the first gain change in the segment, or INT32_MAX */
-    uint32_t npatch;             /* patched samples of the channel inside the segment            */
-    uint32_t pad;
-};
-
-__global__ void gss_linseg_kernel(const gss_lin_t *__restrict__ lin,
-                                  const gss_chan_blk_t *__restrict__ blk,
-                                  const int32_t *__restrict__ nch, const int32_t *__restrict__ fast,
-                                  int nblk, int nseg, lin_seg *__restrict__ seg_out,
-                                  lin_chan *__restrict__ chan_out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nblk * GSS_MAXCH * nseg)
-        return;
-    const int sg = i % nseg, bk = i / nseg, b = bk / GSS_MAXCH, k = bk % GSS_MAXCH;
-    if (!fast[b] || k >= nch[b])
-        return;
-    const gss_lin_t *L = lin + bk;
-    const uint64_t xa = gss_lin_xa(L->xs);
-    if (sg == 0) {
-        lin_chan c;
-        c.xs = L->xs;
-        c.zs = L->zs;
-        c.d = ((uint64_t)gss_lin_dx(L->xs) << 32) | gss_lin_dz(L->zs);
-        c.dq = (uint32_t)((L->zs * 64u) >> 46);
-        c.tab = (uint32_t)blk[bk].ca_tbl;
-        chan_out[bk] = c;
-    }
-    const uint64_t n0 = (uint64_t)sg * (64 * LIN_STEPS);
-    const uint64_t lo = L->z0 + n0 * L->zs;
-    const uint64_t hi = __umul64hi(n0, L->zs) + (lo < L->z0 ? 1u : 0u);
-    const uint32_t E0 = gss_lin_e0((hi << 14) | (lo >> 50));
-    lin_seg r;
-    r.z = (((uint64_t)E0 << 50) | (lo & ((1ull << 50) - 1))) + gss_lin_za(L->zs);
-    r.x = L->x0 + n0 * L->xs + xa;
-    int q = 0;
-    while (q + 1 < GSS_NGC && L->gpos[q + 1] <= (int)n0)
-        q++;
-    const int g0 = L->gval[q];
-    const bool more = q + 1 < GSS_NGC && L->gpos[q + 1] < (int)n0 + 64 * LIN_STEPS;
-    const int g1 = more ? L->gval[q + 1] : g0;
-    r.g01 = (int32_t)(((uint32_t)g0 & 0xFFFFu) | ((uint32_t)g1 << 16));
-    r.pos1 = more ? L->gpos[q + 1] : INT32_MAX;
-    int np = 0;
-    for (int j = 0; j < GSS_NPATCH; j++)
-        np += L->ppos[j] >= (int)n0 && L->ppos[j] < (int)n0 + 64 * LIN_STEPS;
-    r.npatch = (uint32_t)np;
-    r.pad = 0;
-    seg_out[i] = r;
-}
+/* the rows a wave starts from -- per (channel, wave segment) the lines at the segment start, per
+   channel the step constants -- are gss_lin.h's gss_lin_row and gss_lin_chan: gss_lin_kernel
+   builds its workgroup's LIN_WAVES x GSS_MAXCH rows in LDS during its set-up, one lane each */
+typedef gss_lin_row lin_seg;
+typedef gss_lin_chan lin_chan;
+static_assert(sizeof(lin_seg) == 32 && sizeof(lin_chan) == 32, "two 16-byte LDS reads each");
 
 /* per C/A row, the chip-sign bit-stream extended cyclically: bit j of the row = sign of extended
    chip j - 32 (chip (j - 32) mod 1023, 1 = codeCA -1) */
@@ -902,7 +844,7 @@ __device__ __forceinline__ lin_half4 lin_gain_operand(uint32_t gh, int lane)
     return __builtin_bit_cast(lin_half4, v);
 }
 
-__device__ __forceinline__ uint32_t lin_f16_bits(int g)
+__host__ __device__ __forceinline__ uint32_t lin_f16_bits(int g)
 {
     return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)(float)g);
 }
@@ -1078,30 +1020,67 @@ __device__ __forceinline__ void lin_patch_fix(lin_f4 (&cq)[LIN_CH / 2],
 template <int FMT>
 __global__ __launch_bounds__(LIN_THREADS, LIN_MINB) __attribute__((amdgpu_num_sgpr(LIN_SW_SGPRS)))
 void gss_lin_kernel(
-    const gss_lin_t *__restrict__ lin, const lin_seg *__restrict__ segs,
-    const lin_chan *__restrict__ chans, const int32_t *__restrict__ nch,
-    const int32_t *__restrict__ fast, const uint32_t *__restrict__ cab,
-    const uint32_t *__restrict__ tw, lut_arg lut, int n_per_blk, int nseg, int wg_per_blk,
+    const gss_lin_t *__restrict__ lin, const gss_chan_blk_t *__restrict__ blk,
+    const int32_t *__restrict__ nch, const int32_t *__restrict__ fast,
+    const uint32_t *__restrict__ cab, const uint32_t *__restrict__ tw,
+    const uint4 *__restrict__ lut16, int n_per_blk, int wg_per_blk,
     uint8_t *__restrict__ out, size_t block_bytes)
 {
-    __shared__ int32_t s_lut[1024];                       /* (cos, sin) f16; [512+i] = -[i] */
+    __shared__ alignas(16) int32_t s_lut[1024];           /* (cos, sin) f16; [512+i] = -[i] */
     __shared__ uint64_t s_lane[GSS_MAXCH * 64];           /* lane offsets L(l) per channel    */
     __shared__ lin_ct s_ct[LIN_WAVES][GSS_MAXCH];         /* the current chunk, per wave      */
+    __shared__ alignas(16) lin_seg s_seg[LIN_WAVES][GSS_MAXCH];   /* the waves' segment rows  */
+    __shared__ alignas(16) lin_chan s_chan[GSS_MAXCH];    /* the block's channel constants    */
     const int b = blockIdx.x / wg_per_blk;
     const int w = blockIdx.x - b * wg_per_blk;
     if (!fast[b])
         return;                                           /* the exact path renders it */
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);    /* wave-uniform: scalar */
-    for (int i = tid; i < 512; i += LIN_THREADS) {
-        const uint32_t v = lin_f16_bits(lut.cos512[i]) | (lin_f16_bits(lut.sin512[i]) << 16);
-        s_lut[i] = (int32_t)v;
-        s_lut[512 + i] = (int32_t)(v ^ 0x80008000u);
-    }
-    const lin_chan *CH = chans + (size_t)b * GSS_MAXCH;
+    static_assert(sizeof(s_lut) == LIN_THREADS * sizeof(uint4), "one 16-byte copy per thread");
+    const uint4 lutv = lut16[tid];          /* the packed LUT (gss_dev_open); stored below, so
+                                               that its load is in flight beside the lines'  */
+    const gss_lin_t *L = lin + (size_t)b * GSS_MAXCH;
     const int nc = nch[b];
-    for (int i = tid; i < nc * 64; i += LIN_THREADS)
-        s_lane[i] = gss_lin_lane(CH[i >> 6].xs, CH[i >> 6].zs, (uint32_t)(i & 63));
+    /* the lane table: wave j makes channels j, j + LIN_WAVES, ... (wave-uniform: the lines'
+       steps come by scalar loads) */
+#pragma unroll
+    for (int j = 0; j < GSS_MAXCH / LIN_WAVES; j++) {
+        const int k = wave + j * LIN_WAVES;
+        if (k < nc)
+            s_lane[k * 64 + lane] = gss_lin_lane(L[k].xs, L[k].zs, (uint32_t)lane);
+    }
+    /* the workgroup's rows (gss_lin.h): lane 16 j + k stands for wave j's row of channel k, and
+       each wave makes one part of all 64 rows -- wave 0 the anchor bases, wave 1 the gain pair,
+       wave 2 the patch count, wave 3 (for the first 16 lanes) the channel's constants -- so that
+       no instruction stream runs twice and no wave makes a whole row alone.  The lanes of
+       channels past nc and of segments past the block's end make nothing (those lanes and
+       waves take no row below) */
+    {
+        const int rk = lane & (GSS_MAXCH - 1), rj = lane / GSS_MAXCH;
+        static_assert(LIN_WAVES * GSS_MAXCH == 64 && LIN_WAVES == 4, "one row per lane, 4 parts");
+        const int rn0 = (w * LIN_WAVES + rj) * (64 * LIN_STEPS);
+        if (rk < nc && rn0 < n_per_blk) {
+            const gss_lin_t *Lk = L + rk;
+            lin_seg &r = s_seg[rj][rk];
+            if (wave == 0) {
+                r.x = gss_lin_row_x(Lk->x0, Lk->xs, (uint64_t)rn0);
+                r.z = gss_lin_row_z(Lk->z0, Lk->zs, (uint64_t)rn0);
+            } else if (wave == 1) {
+                gss_lin_row g;
+                gss_lin_row_gain(&g, Lk->gpos, Lk->gval, GSS_NGC, rn0);
+                r.g01 = g.g01;
+                r.pos1 = g.pos1;
+            } else if (wave == 2) {
+                r.npatch = gss_lin_row_npatch(Lk->ppos, GSS_NPATCH, rn0);
+                r.pad = 0;
+            } else if (rj == 0) {
+                s_chan[rk] = gss_lin_chan_of(Lk->xs, Lk->zs,
+                                             (uint32_t)blk[(size_t)b * GSS_MAXCH + rk].ca_tbl);
+            }
+        }
+    }
+    ((uint4 *)s_lut)[tid] = lutv;
     (void)cab;
     __syncthreads();
     uint32_t M = 0xFFCu;                                  /* LUT address mask, in a VGPR */
@@ -1113,8 +1092,6 @@ void gss_lin_kernel(
     const int n0 = sg * (64 * LIN_STEPS);
     if (n0 >= n_per_blk)
         return;
-    const gss_lin_t *L = lin + (size_t)b * GSS_MAXCH;
-    const lin_seg *S = segs + (size_t)b * GSS_MAXCH * nseg + sg;
     lin_ct *T = s_ct[wave];
     uint8_t *ob = out + (size_t)b * block_bytes;
     bool sw_ahead = false;                 /* the chunk's first pair is already loading */
@@ -1126,8 +1103,8 @@ void gss_lin_kernel(
     uint32_t trow = 0, wa_next = 0;                    /* table row base, this chunk's row     */
     int g_after = -1;                                  /* the gain the record holds (none yet) */
     if (lane < nc) {
-        const lin_chan ck = CH[lane];
-        const lin_seg sk = S[(size_t)lane * nseg];
+        const lin_chan ck = s_chan[lane];
+        const lin_seg sk = s_seg[wave][lane];
         xb = sk.x;
         zb = sk.z;
         xs10 = ck.xs << 10;
@@ -1302,11 +1279,12 @@ struct gss_dev {
     hipEvent_t ev_l[RING][2];                  /* ... and of each fast-path launch         */
     int n_a = 0, n_b = 0, n_l = 0;
     lut_arg lut;
+    uint4 *d_lut16 = nullptr;            /* the fast kernel's LUT: (cos, sin) f16 pairs, the
+                                            second half negated; made once (gss_dev_open)  */
     void *h_in = nullptr; size_t h_in_cap = 0;
     void *d_out = nullptr; size_t d_out_cap = 0;
     double *d_cend = nullptr; size_t d_cend_cap = 0;
     uint32_t *d_cbw = nullptr; size_t d_cbw_cap = 0;   /* chip-sign bit-streams (gss_cab_kernel) */
-    void *d_seg = nullptr; size_t d_seg_cap = 0;       /* lin_seg rows (gss_linseg_kernel)   */
     int32_t *d_status = nullptr;
     /* the exact path's leftovers of a fast-path call run on their own stream beside the fast
        kernel (a few latency-bound blocks would otherwise serialise after it) */
@@ -1364,6 +1342,16 @@ extern "C" int gss_dev_open(gss_dev **out, int ordinal)
         d->lut.sin512[i] = (int16_t)s[i];
         d->lut.cos512[i] = (int16_t)c[i];
     }
+    {
+        uint32_t packed[1024];
+        for (int i = 0; i < 512; i++) {
+            const uint32_t v = lin_f16_bits(c[i]) | (lin_f16_bits(s[i]) << 16);
+            packed[i] = v;
+            packed[512 + i] = v ^ 0x80008000u;
+        }
+        HIP_TRY(hipMalloc(&d->d_lut16, sizeof(packed)));
+        HIP_TRY(hipMemcpy(d->d_lut16, packed, sizeof(packed), hipMemcpyHostToDevice));
+    }
     HIP_TRY(hipMalloc(&d->d_status, sizeof(int32_t)));
     int prio_lo = 0, prio_hi = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
@@ -1390,7 +1378,7 @@ extern "C" int gss_dev_close(gss_dev *d)
     if (d->aux) (void)hipStreamDestroy(d->aux);
     if (d->ev_in) (void)hipEventDestroy(d->ev_in);
     if (d->ev_fb) (void)hipEventDestroy(d->ev_fb);
-    void *bufs[] = {d->h_in, d->d_out, d->d_cend, d->d_cbw, d->d_seg, d->d_status};
+    void *bufs[] = {d->h_in, d->d_out, d->d_cend, d->d_cbw, d->d_lut16, d->d_status};
     for (void *p : bufs)
         (void)hipFree(p);
     for (int i = 0; i < gss_dev::RING; i++)
@@ -1550,8 +1538,8 @@ extern "C" int gss_render_device(gss_dev *d, int set, const gss_chan_blk_t *blk,
 }
 
 /* ---- fast path -------------------------------------------------------------------------- */
-typedef void (*lin_fn)(const gss_lin_t *, const lin_seg *, const lin_chan *, const int32_t *,
-                       const int32_t *, const uint32_t *, const uint32_t *, lut_arg, int, int,
+typedef void (*lin_fn)(const gss_lin_t *, const gss_chan_blk_t *, const int32_t *,
+                       const int32_t *, const uint32_t *, const uint32_t *, const uint4 *, int,
                        int, uint8_t *, size_t);
 
 static lin_fn pick_lin(int fmt)
@@ -1607,21 +1595,6 @@ extern "C" int gss_synth_lin_device(gss_dev *d, const gss_chan_blk_t *blk, const
     HIP_TRY(hipGetLastError());
     const int segs = (n_per_blk + 64 * LIN_STEPS - 1) / (64 * LIN_STEPS);
     const int wg_per_blk = (segs + LIN_WAVES - 1) / LIN_WAVES;
-    const size_t nsegrows = (size_t)nblk * GSS_MAXCH * segs;
-    const size_t seg_bytes = nsegrows * sizeof(lin_seg);
-    const size_t need_rows = seg_bytes + (size_t)nblk * GSS_MAXCH * sizeof(lin_chan);
-    if (need_rows > d->d_seg_cap) {
-        (void)hipFree(d->d_seg);
-        d->d_seg = nullptr;
-        d->d_seg_cap = 0;
-        HIP_TRY(hipMalloc(&d->d_seg, need_rows));
-        d->d_seg_cap = need_rows;
-    }
-    lin_seg *d_segs = (lin_seg *)d->d_seg;
-    lin_chan *d_chans = (lin_chan *)((char *)d->d_seg + seg_bytes);
-    hipLaunchKernelGGL(gss_linseg_kernel, dim3((unsigned)((nsegrows + 255) / 256)), dim3(256), 0,
-                       st, lin, blk, nch, fast, nblk, segs, d_segs, d_chans);
-    HIP_TRY(hipGetLastError());
     if (n_fb > 0) {          /* the exact path for the uncertified blocks, on the aux stream */
         HIP_TRY(hipEventRecord(d->ev_in, st));
         HIP_TRY(hipStreamWaitEvent(d->aux, d->ev_in, 0));
@@ -1639,8 +1612,8 @@ extern "C" int gss_synth_lin_device(gss_dev *d, const gss_chan_blk_t *blk, const
     d->n_l++;
     HIP_TRY(hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(fn, dim3((unsigned)nblk * wg_per_blk), dim3(LIN_THREADS), 0, st, lin,
-                       (const lin_seg *)d_segs, (const lin_chan *)d_chans, nch, fast, d->d_cbw,
-                       d->d_cbw + tw_off, d->lut, n_per_blk, segs, wg_per_blk, (uint8_t *)out, bb);
+                       blk, nch, fast, d->d_cbw, d->d_cbw + tw_off, (const uint4 *)d->d_lut16,
+                       n_per_blk, wg_per_blk, (uint8_t *)out, bb);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[1], st));
     if (n_fb > 0)                                 /* the call completes when both are done */
