@@ -1222,6 +1222,10 @@ GSS_HD double gss_walk_margins_cc(double x, double s, int64_t n, double *dlo, do
     cc->next = 0;
     cc->last = -1;
     cc->enabled = 1;
+    /* a start off the post-wrap lattice (a given segment start: the walkers' own are on it) is no
+       lattice translation of any later cycle's: its cycle, the first, is not cached */
+    const double q = x * (s > 0.0 ? 0x1p52 : 0x1p53);
+    int on = q == GSS_FLOOR(q);
     if (s > 0.0) {
         while (left > 0) {
             const double w = x;
@@ -1242,7 +1246,8 @@ GSS_HD double gss_walk_margins_cc(double x, double s, int64_t n, double *dlo, do
             last = wr;
             if (clo > *dlo) *dlo = clo;
             if (chi < *dhi) *dhi = chi;
-            if (wr) gss_cc_put(cc, w, clo, chi, safe, x, taken);
+            if (wr && on) gss_cc_put(cc, w, clo, chi, safe, x, taken);
+            on = 1;
         }
         *wrap_end = last;
         return x;
@@ -1268,8 +1273,9 @@ GSS_HD double gss_walk_margins_cc(double x, double s, int64_t n, double *dlo, do
             if (chi < *dhi) *dhi = chi;
             if (!st || left <= 0)
                 break;
-            gss_cc_put(cc, w, clo, chi, safe, x, taken);
+            if (on) gss_cc_put(cc, w, clo, chi, safe, x, taken);
         }
+        on = 1;
         while (left > 0) {                      /* below T: real steps to the wrap */
             gss_margin_step(x, s, dunit, dlo, dhi);
             const double r = x + s;
@@ -1350,7 +1356,12 @@ GSS_HD void gss_spec_guess_row(double g, double s, int64_t n, gss_spec_in_t *in)
     in->k = k;
 }
 
-/* Segment j of a row's walk (n samples per block). */
+/* Segment j of a row's walk (n samples per block).  A walked segment's interval holds 0 (the
+   walked start itself) or is left empty: the conservative margins can leave 0 out where a value
+   lands exactly on a binade's lower end (gss_margin_step_carr: lo = one ulp) or a descending wrap
+   falls within two units of 0 (lim = -r - 2 dunit), as with a power-of-two step from a start on
+   its lattice; such an interval carries no translation the chain could use (its fix-up tests d
+   against it and walks), so it is not reported as one. */
 GSS_HD void gss_spec_seg_walk(const gss_spec_in_t *in, int j, int64_t n, gss_spec_t *o)
 {
     const double s = in->s;
@@ -1388,9 +1399,11 @@ GSS_HD void gss_spec_seg_walk(const gss_spec_in_t *in, int j, int64_t n, gss_spe
     x = gss_walk_margins(x, s, stop - pos, &dlo, &dhi, &we);
 #endif
     sg->end = x;
-    sg->dlo = dlo;
-    sg->dhi = dhi;
     sg->wrap_end = we;
+    if (dlo <= 0.0 && dhi >= 0.0) {             /* else no interval: see above */
+        sg->dlo = dlo;
+        sg->dhi = dhi;
+    }
 }
 
 /* The exact walk from v at sample pos to the block end, through the segment starts P[j] (j >= j0)

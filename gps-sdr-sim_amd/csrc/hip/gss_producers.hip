@@ -113,7 +113,9 @@ __device__ inline int spec_row_of(int u, int nrow)
  * The cache: SC_N entries per row in LDS (start interval [lo, hi], end offset dv = v0 - w0, steps
  * L) and SC_NB buckets over the row's post-wrap range (|s| wide) of the last two entries that
  * cover each; a lookup reads one bucket and tests at most two entries.  A stale bucket slot only
- * misses (an entry is used only when its own interval holds the start).  Host model of the
+ * misses (an entry is used only when its own interval holds the start).  Entries are made from
+ * and used for starts on the post-wrap lattice only (every start but a given W[j] off it: `raw`):
+ * end = x + dv is exact between lattice points alone.  Host model of the
  * schedule (miss rounds 4-5 per wave against 11-12 cycle walks, headline rows): DESIGN.md §7.1.
  * The intervals differ from the host walk's (gss_spec_seg_walk) by the cache's `safe` shrink and
  * the entries' own margins: the tests compare ends, wraps and p1/w1 bit for bit and require the
@@ -191,7 +193,7 @@ __device__ void sc_seg_walk(double g, double s, int64_t Pj, double Wj, int64_t s
                             int64_t n, sc_res *res, bool walk, spec_cc *cc)
 {
     gss_spec_seg_t *sg = &res->sg;
-    bool act = false;
+    bool act = false, raw = false;
     double x = 0.0;
     int64_t left = 0;
     if (walk) {
@@ -213,6 +215,11 @@ __device__ void sc_seg_walk(double g, double s, int64_t Pj, double Wj, int64_t s
             pos = Pj;
             sg->end = x;
             act = s != 0.0 && pos < stop;
+            /* a given start off the post-wrap lattice (the walkers' own guesses are on it): its
+               first cycle is no lattice translation of any other, so it is walked and not
+               shared; the wrap puts the walk on the lattice */
+            const double q = x * (s > 0.0 ? 0x1p52 : 0x1p53);
+            raw = q != __builtin_floor(q);
         }
         left = stop - pos;
 #ifdef SC_SKIP
@@ -249,7 +256,7 @@ __device__ void sc_seg_walk(double g, double s, int64_t Pj, double Wj, int64_t s
             const int32_t L0 = cc->L[a0], L1 = cc->L[a1];
             const bool ok0 = i0 >= 0 && x >= lo0 && x <= hi0 && L0 <= left;
             const bool ok1 = i1 >= 0 && x >= lo1 && x <= hi1 && L1 <= left;
-            if (ok0 || ok1) {
+            if ((ok0 || ok1) && !raw) {
                 const double lo = (ok0 ? lo0 : lo1) - x, hi = (ok0 ? hi0 : hi1) - x;
                 if (lo > dlo) dlo = lo;
                 if (hi < dhi) dhi = hi;
@@ -279,7 +286,9 @@ __device__ void sc_seg_walk(double g, double s, int64_t Pj, double Wj, int64_t s
             blocked = false;
             if (left <= 0)
                 act = false;
-            if (wr && clo <= 0.0 && chi >= 0.0 && t <= INT32_MAX) {
+            const bool share = !raw;
+            raw = false;
+            if (wr && share && clo <= 0.0 && chi >= 0.0 && t <= INT32_MAX) {
                 const int i = atomicAdd(&cc->next, 1) % SC_N;
                 double lo = w + clo + safe, hi = w + chi - safe;
                 if (lo > w) lo = w;                   /* the walked start itself is valid */
@@ -296,9 +305,10 @@ __device__ void sc_seg_walk(double g, double s, int64_t Pj, double Wj, int64_t s
         __syncthreads();                              /* one wave: the entries before the lookups */
     }
     if (walked) {
+        const bool has0 = dlo <= 0.0 && dhi >= 0.0;   /* else no interval (gss_spec_seg_walk) */
         sg->end = x;
-        sg->dlo = dlo;
-        sg->dhi = dhi;
+        sg->dlo = has0 ? dlo : 1.0;
+        sg->dhi = has0 ? dhi : 0.0;
         sg->wrap_end = last;
     }
 }

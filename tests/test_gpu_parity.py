@@ -22,6 +22,7 @@ from conftest import CIRCLE, LOC, NAV
 
 import gpssim_amd as G
 import oracle
+from spec_oracle import _spec_walks_agree
 
 pytestmark = pytest.mark.gpu
 
@@ -504,29 +505,6 @@ def test_producers_on_device(dev, golden):
                             len(src) - cut, rows.data_ptr())
         torch.cuda.synchronize()
         assert np.array_equal(rows.cpu().numpy().view(np.uint32), want), kw
-
-
-def _spec_walks_agree(got, want, gi, kw):
-    """The device's walks against the host's (gss_spec_host): the same ends, wraps and first wraps
-    bit for bit, and each segment's interval of exact start translations inside the host's (the
-    device walks cycles from a cache its row's lanes share, whose entries' intervals are narrower:
-    gss_producers.hip, sc_seg_walk); padding rows are not walked."""
-    live = gi.reshape(-1)["s"] != 0
-    assert np.array_equal(got["p1"][live], want["p1"][live]), kw
-    assert np.array_equal(got["w1"][live], want["w1"][live]), kw
-    narrower = 0
-    for r in np.flatnonzero(live):
-        k = gi.reshape(-1)["k"][r]
-        g, w = got["seg"][r][:k], want["seg"][r][:k]
-        assert g["end"].tobytes() == w["end"].tobytes(), (kw, r)
-        assert np.array_equal(g["wrap_end"], w["wrap_end"]), (kw, r)
-        empty = w["dlo"] > w["dhi"]                      # not walked: the same empty interval
-        assert g[empty].tobytes() == w[empty].tobytes(), (kw, r)
-        assert np.all(g["dlo"][~empty] >= w["dlo"][~empty]), (kw, r)
-        assert np.all(g["dhi"][~empty] <= w["dhi"][~empty]), (kw, r)
-        assert np.all(g["dlo"][~empty] <= 0) and np.all(g["dhi"][~empty] >= 0), (kw, r)
-        narrower += int(np.sum((g["dlo"] != w["dlo"]) | (g["dhi"] != w["dhi"])))
-    return narrower
 
 
 def test_spec_walks_on_device(dev):
