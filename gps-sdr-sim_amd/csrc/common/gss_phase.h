@@ -85,6 +85,9 @@ GSS_HD int64_t gss_jump(double v, double s, double W, double *D)
     gss_bits64 b;
     b.d = v;
     if (b.u >> 63) return 0;                      /* negative or -0 */
+    if (v >= W) return 0;                         /* exactly W (carr0 == 1.0, or a descending wrap
+                                                     whose + 1.0 rounded up): the real step wraps,
+                                                     also where |s| < u/2 would call v stationary */
     int E = (int)((b.u >> 52) & 0x7FF);
     if (E < 64 || E == 0x7FF) return 0;          /* zero / tiny / non-finite: take real steps */
     int64_t m = (int64_t)((b.u & 0xFFFFFFFFFFFFFull) | (1ull << 52));   /* v = m*u */
@@ -423,12 +426,18 @@ GSS_HD int gss_trip(int kind, double *pv, double s, double rs, double *pleft, do
 #ifndef GSS_CARR_MACRO
 #define GSS_CARR_MACRO 8         /* real carrier steps near a wrap (gss_seg_states) */
 #endif
-/* one reference carrier step (gpssim.c:2245-2250): on the GPU v_fract_f64 of the sum, which is
-   exactly carr-1 / carr+1 for sums in [0,2) / (-1,1) */
+/* one reference carrier step (gpssim.c:2245-2250) of a chain of the given kind.  On the GPU the
+   wrap of the sum r is r - floor(r), exactly r-1 / r+1 for r in [0,2) / (-1,1) (DESIGN.md §4.2;
+   r == 2.0 needs carr0 == 1.0 with carr_step == 1 - 2^-53, which gss_synth_host refuses).  An
+   ascending chain may take v_fract_f64 instead (r >= 0: its result is exact and below 1); a
+   descending one may not: v_fract_f64 clamps its result below 1, where the reference's r + 1.0
+   rounds to 1.0 for r in [-2^-54, 0). */
+GSS_HD double gss_carr_wrap(double r) { return r - GSS_FLOOR(r); }
 #if defined(__HIP_DEVICE_COMPILE__)
-#define GSS_CARR_STEP(v, s) __builtin_amdgcn_fract((v) + (s))
+#define GSS_CARR_STEP(kind, v, s) \
+    ((kind) == GSS_TRIP_CARR_ASC ? __builtin_amdgcn_fract((v) + (s)) : gss_carr_wrap((v) + (s)))
 #else
-#define GSS_CARR_STEP(v, s) gss_carr_step1((v), (s))
+#define GSS_CARR_STEP(kind, v, s) gss_carr_step1((v), (s))
 #endif
 
 /* Exact states at the segment starts n0 = j*seg_r in [pos0, pos1) of one chain (j < nseg),
@@ -444,13 +453,13 @@ GSS_HD double gss_seg_states(int kind, double v, double st, uint32_t cnt, int po
 {
     const int code = kind == GSS_TRIP_CODE;
     const double rs = 1.0 / (st < 0.0 ? -st : st);
-    const double p0 = (double)pos0, total = (double)(pos1 - pos0), R = (double)seg_r;
+    const double R = (double)seg_r;
+    double total = (double)(pos1 - pos0);
     int seg = (pos0 + seg_r - 1) / seg_r;               /* first segment start >= pos0 */
     int seg_hi = (pos1 + seg_r - 1) / seg_r;            /* segment starts < pos1 */
     if (seg_hi > nseg)
         seg_hi = nseg;
-    double left = st == 0.0 ? 0.0 : total;             /* no motion: no wraps */
-    double n0 = (double)seg * R - p0;                   /* next segment start, relative */
+    double n0 = (double)seg * R - (double)pos0;         /* next segment start, relative */
     if (seg < seg_hi && n0 == 0.0) {                    /* a segment starts at pos0 */
         out_x[seg] = v;
         if (code)
@@ -458,6 +467,20 @@ GSS_HD double gss_seg_states(int kind, double v, double st, uint32_t cnt, int po
         seg++;
         n0 += R;
     }
+    /* A carrier of exactly 1.0 (carr0 == 1.0 is a valid row; a descending wrap's + 1.0 can round
+       up to it) is no lattice start: the reference's next step is 1 + st >= 1 -> - 1, also for
+       st == 0.  Take that step for real and walk on from position pos0 + 1. */
+    if (!code && v >= 1.0 && total > 0.0) {
+        v = GSS_CARR_STEP(GSS_TRIP_CARR_DESC, v, st);   /* r - floor(r): right for both signs */
+        total -= 1.0;
+        n0 -= 1.0;
+        if (seg < seg_hi && n0 == 0.0) {
+            out_x[seg] = v;
+            seg++;
+            n0 += R;
+        }
+    }
+    double left = st == 0.0 ? 0.0 : total;             /* no motion: no wraps */
     if (left == 0.0)
         for (; seg < seg_hi; seg++) {
             out_x[seg] = v;
@@ -467,7 +490,20 @@ GSS_HD double gss_seg_states(int kind, double v, double st, uint32_t cnt, int po
     while (left > 0.0 && (seg < seg_hi || want_end)) {
         const double vb = v, pb = total - left;
         double J, Ds;
-        const int wr = gss_trip(kind, &v, st, rs, &left, &J, &Ds);
+        double vt = v, lt = left;
+        const int wr = gss_trip(kind, &vt, st, rs, &lt, &J, &Ds);
+        if (kind == GSS_TRIP_CARR_DESC) {
+            /* exactly 1.0 again (a descending wrap's + 1.0 rounded up; an ascending chain stays
+               below 1 after the step above): one real step and no jump, as selects */
+            const int one = v >= 1.0;
+            const double vs = GSS_CARR_STEP(kind, v, st);
+            vt = one ? vs : vt;
+            lt = one ? left - 1.0 : lt;
+            J = one ? 0.0 : J;
+            Ds = one ? 0.0 : Ds;
+        }
+        v = vt;
+        left = lt;
         const double pa = total - left;
         const uint32_t cnt_b = cnt;
         if (code & wr) {                                /* gpssim.c:2216-2236 */
@@ -502,7 +538,7 @@ GSS_HD double gss_seg_states(int kind, double v, double st, uint32_t cnt, int po
             const double as = st < 0.0 ? -st : st;
             double vm = v;
             for (int i = 0; i < GSS_CARR_MACRO; i++)
-                vm = GSS_CARR_STEP(vm, st);
+                vm = GSS_CARR_STEP(kind, vm, st);
             const double lo = kind == GSS_TRIP_CARR_ASC ? as : (double)GSS_CARR_MACRO * as;
             const int mac = (v < lo) & (left > (double)GSS_CARR_MACRO) &
                             ((seg >= seg_hi) | (n0 > pa + (double)GSS_CARR_MACRO));
@@ -642,8 +678,8 @@ GSS_HD double gss_walk_bf(double x, double s, double W, double n, int *nwrap)
 /* Advance the carrier recurrence by n steps, exactly. */
 GSS_HD double gss_carr_walk(double x, double s, int64_t n)
 {
-    if (s == 0.0)                                /* x + 0 == x: nothing moves */
-        return x;
+    if (s == 0.0)                                /* x + 0 == x: nothing moves, but 1.0 wraps */
+        return n > 0 && x >= 1.0 ? x - 1.0 : x;
     while (n > 0) {
         double D;
         int64_t J = gss_jump(x, s, 1.0, &D);
@@ -1001,6 +1037,15 @@ GSS_HD int gss_carr_plain_to_wrap(gss_carr_it *it)
 GSS_HD int gss_carr_next_wrap(gss_carr_it *it)
 {
     if (it->left <= 0) return 0;
+    if (it->x >= 1.0) {
+        /* exactly 1.0 (a block start, or a descending wrap whose + 1.0 rounded up) is no lattice
+           start of a cycle: the reference's own step (1 + s >= 1 wraps), then the plain walk */
+        it->x = gss_carr_step1(it->x, it->s);
+        it->pos++;
+        it->left--;
+        it->mid = 1;
+        return 1;
+    }
     if (it->mid || !it->cc.enabled) {
         it->mid = 0;
         return gss_carr_plain_to_wrap(it);

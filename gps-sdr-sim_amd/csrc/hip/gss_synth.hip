@@ -14,7 +14,7 @@
  * Stage B  gss_synth_kernel     one lane per R-sample segment of a block, all channels.  Each lane
  *                               first walks every channel from its anchor to the segment start
  *                               (≤ one cycle, no wrap), then runs the per-sample recurrences:
- *                               carrier via v_fract_f64, chip sign from a byte table, data-bit
+ *                               carrier via r - floor(r), chip sign from a byte table, data-bit
  *                               sign folded into the gain, LUT[floor(512 carr)] x gain summed
  *                               over channels with v_dot2 on packed int16, (acc+64)>>7,
  *                               SC16/SC08/SC01 packing.  Output is staged per lane in LDS
@@ -267,6 +267,7 @@ __global__ __launch_bounds__(SYNTH_THREADS) __attribute__((amdgpu_waves_per_eu(S
     int len = active ? n_per_blk - n0 : 0;
     if (len > seg_r) len = seg_r;
     const int segc = active ? seg : nseg - 1;           /* inactive lanes: any valid anchor */
+    const bool last_seg = seg == nseg - 1;              /* this lane renders the block's end  */
 
     /* block-uniform channel steps (scalar registers); padding channels: no motion, no gain.
        Gains are re-read (scalar loads) where a data bit changes, to spare scalar registers. */
@@ -322,6 +323,11 @@ __global__ __launch_bounds__(SYNTH_THREADS) __attribute__((amdgpu_waves_per_eu(S
     for (int ch = 0; ch < wave_chunks; ch++) {
         const bool full = ch < nchunk;
         const int nsamp = full ? SPC : (ch == nchunk ? len - nchunk * SPC : 0);
+        /* samples whose lazy wrap counts for the status: a wrap made by the add of sample s is
+           applied at s + 1, so the block's last add (the last segment's sample len - 1, which
+           the reference counts, gpssim.c:2229-2232) shows at sample nsamp of the lane's last
+           chunk, or after the chunk when that one is full (below) */
+        const int nchk = nsamp + (last_seg && nsamp > 0 ? 1 : 0);
         uint32_t bits = 0;
 #pragma unroll 1
         for (int sidx = 0; sidx < SPC; sidx++) {
@@ -373,7 +379,7 @@ __global__ __launch_bounds__(SYNTH_THREADS) __attribute__((amdgpu_waves_per_eu(S
                         if (nbit) {
                             icode = 0;
                             if (++ibit >= 30) { ibit = 0; iword++; }
-                            if (iword > 59) { bad |= (wk && sidx < nsamp) ? 1 : 0; iword = 59; }
+                            if (iword > 59) { bad |= (wk && sidx < nchk) ? 1 : 0; iword = 59; }
                         }
                         const uint32_t c2 = (uint32_t)icode | ((uint32_t)ibit << 5) |
                                             ((uint32_t)iword << 10);
@@ -418,10 +424,11 @@ __global__ __launch_bounds__(SYNTH_THREADS) __attribute__((amdgpu_waves_per_eu(S
             }
 #pragma unroll
             for (int k = 0; k < NCH; k++) {
-                /* carrier (gpssim.c:2245-2250): carr+s is in [0,2) ascending or (-1,1)
-                   descending, where v_fract_f64 returns exactly the reference's carr-1 / carr+1
-                   (x - floor(x), one IEEE rounding) */
-                carr[k] = __builtin_amdgcn_fract(carr[k] + cs[k]);
+                /* carrier (gpssim.c:2245-2250): r = carr+s is in [0,2) ascending or (-1,1)
+                   descending, where r - floor(r) is exactly the reference's r-1 / r+1 (one IEEE
+                   rounding).  Not v_fract_f64: it clamps its result below 1, and the reference's
+                   r + 1.0 rounds to 1.0 for r in [-2^-54, 0) */
+                carr[k] = gss_carr_wrap(carr[k] + cs[k]);
                 C[k] = C[k] + ks[k];                          /* code (gpssim.c:2212) */
             }
             /* gpssim.c:2257-2263: (acc+64)>>7 (arithmetic), then (short).  Written
@@ -443,6 +450,14 @@ __global__ __launch_bounds__(SYNTH_THREADS) __attribute__((amdgpu_waves_per_eu(S
                     mine[sidx >> 4] = __builtin_bswap32(w32);
                     bits = 0;
                 }
+            }
+        }
+        if (last_seg && full && (ch + 1) * SPC == len) {
+            /* the block ends with this full chunk: a wrap its last add made is still pending */
+#pragma unroll
+            for (int k = 0; k < NCH; k++) {
+                const uint32_t c = s_st[k][tid];
+                bad |= (C[k] >= GSS_CA_SEQ_LEN_D && c == (19u | (29u << 5) | (59u << 10))) ? 1 : 0;
             }
         }
         const bool any_full = __any(full);
@@ -1721,7 +1736,8 @@ extern "C" int gss_synth_host(gss_dev *d, const gss_chan_blk_t *blk, const int32
                 p->iword >= GSS_NAV_WORDS || !(p->code0 >= 0.0 && p->code0 < 1023.0) ||
                 !(p->carr0 >= 0.0 && p->carr0 <= 1.0) ||
                 !(p->code_step > 0.0 && p->code_step < 1023.0) ||
-                !(p->carr_step > -1.0 && p->carr_step < 1.0))
+                !(p->carr_step > -1.0 && p->carr_step < 1.0) ||
+                !(p->carr0 + p->carr_step < 2.0))      /* 1.0 + (1 - 2^-53) rounds to 2.0 */
                 return gss_fail(GSS_E_ARG, "block %d channel %d: parameter out of range", b, k);
             if (carr_ck)
                 for (int j = 0; j < GSS_NCK; j++) {

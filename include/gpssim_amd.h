@@ -101,7 +101,16 @@ size_t gss_block_bytes(int n_per_blk, int fmt);
      out      nblk * gss_block_bytes(n_per_blk, fmt) bytes, exactly the bytes the reference
               fwrite()s for those blocks (gpssim.c:2276/2283/2287), concatenated in block order
      carr_end optional [nblk][GSS_MAXCH]: carrier phase after the block's last sample
-     status   optional int32[1]: set non-zero if a nav-word index ran past 59
+     status   optional int32[1]: set non-zero if a nav-word index ran past 59 on any of a
+              block's n_per_blk code-phase adds, the add of the block's last sample included
+              (the reference counts the wrap in the sample that makes it, gpssim.c:2212-2237),
+              or was past 59 in a row; never cleared (the caller zeroes it)
+     out      needs no alignment (a misaligned base takes narrower stores)
+     carr0    may be exactly 1.0 (what a descending wrap's + 1.0 can round to): the first step
+              is then the reference's 1 + carr_step >= 1 -> - 1, also for carr_step == 0.
+              carr0 + carr_step must stay below 2.0 in double arithmetic: the one row that does
+              not, carr0 == 1.0 with carr_step == 1 - 2^-53, is unsupported here and refused by
+              gss_synth_host (GSS_E_ARG)
    stream is a hipStream_t (NULL = default stream).  Asynchronous; no host synchronisation.    */
 int gss_synth_device(gss_dev *d, const gss_chan_blk_t *blk, const int32_t *nch, int nch_max,
                      const double *carr_ck, const uint32_t *ca_bits, int n_ca, const uint32_t *nav, int n_nav,
