@@ -24,6 +24,7 @@ LIB_PATH = os.environ.get("GSS_LIB_PATH") or _INTREE
 IN_TREE = os.path.abspath(LIB_PATH) == os.path.abspath(_INTREE)
 CLI_PATH = os.path.join(PKG_DIR, "bin", "gps-sdr-sim")
 ACQ_CLI_PATH = os.path.join(PKG_DIR, "bin", "gps-sdr-acq")
+TRK_CLI_PATH = os.path.join(PKG_DIR, "bin", "gps-sdr-track")
 
 MAXCH = 16
 CA_WORDS = 32
@@ -82,6 +83,19 @@ NAV_HEAD_INIT, NAV_HEAD_GIVEN = -1, -2
 ACQ_PEAK_DTYPE = np.dtype([("peak", "<u8"), ("floor_sum", "<u8"), ("floor_cnt", "<u4"),
                            ("tau", "<i4"), ("bin", "<i4"), ("prn", "<i4")])
 assert ACQ_PEAK_DTYPE.itemsize == 32
+# gss_trk_rec_t: one code period of one tracking job (gss_track_*)
+TRK_REC_DTYPE = np.dtype([("IE", "<i8"), ("QE", "<i8"), ("IP", "<i8"), ("QP", "<i8"),
+                          ("IL", "<i8"), ("QL", "<i8"), ("s", "<i8"), ("w", "<i4"),
+                          ("dcs", "<i4")])
+assert TRK_REC_DTYPE.itemsize == 64
+# gss_trk_job_t: where a tracking job starts (gss_trk_job_from_peak)
+TRK_JOB_DTYPE = np.dtype([("s0", "<i8"), ("prn", "<i4"), ("w0", "<i4"), ("n_epoch", "<i4"),
+                          ("pad", "<i4")])
+assert TRK_JOB_DTYPE.itemsize == 24
+# gss_nav_sf_t: one decoded subframe (gss_nav_decode)
+NAV_SF_DTYPE = np.dtype([("sample", "<i8"), ("epoch", "<i4"), ("polarity", "<i4"),
+                         ("tow", "<i4"), ("id", "<i4"), ("word", "<u4", (10,))])
+assert NAV_SF_DTYPE.itemsize == 64
 
 
 class GssError(RuntimeError):
@@ -150,6 +164,25 @@ class Acq(C.Structure):
         return {FMT_SC16: 4 * n, FMT_SC08: 2 * n, FMT_SC01: (n + 3) // 4}[self.fmt]
 
 
+class Trk(C.Structure):
+    """gss_trk_cfg_t: the tracking loops.  Trk(fs_hz, fmt) holds the default gains
+    (gss_trk_defaults); keyword arguments n_pull, Kf, Ki, Kp, Kd replace single fields."""
+    _fields_ = [("fs_hz", C.c_int32), ("fmt", C.c_int32), ("n_pull", C.c_int32),
+                ("Kf", C.c_int32), ("Ki", C.c_int32), ("Kp", C.c_int32), ("Kd", C.c_int32)]
+
+    def __init__(self, fs_hz, fmt=16, **over):
+        super().__init__()
+        _check(lib().gss_trk_defaults(int(fs_hz), int(fmt), C.byref(self)))
+        for k, v in over.items():
+            if k not in ("n_pull", "Kf", "Ki", "Kp", "Kd"):
+                raise TypeError(f"unknown field {k}")
+            setattr(self, k, int(v))
+
+    def __repr__(self):
+        return (f"Trk(fs_hz={self.fs_hz}, fmt={self.fmt}, n_pull={self.n_pull}, Kf={self.Kf}, "
+                f"Ki={self.Ki}, Kp={self.Kp}, Kd={self.Kd})")
+
+
 class _Truth(C.Structure):                           # gss_acq_truth_t
     _fields_ = [("tau", C.c_double), ("doppler_hz", C.c_double), ("cn0_offset_db", C.c_double),
                 ("prn", C.c_int32), ("pad", C.c_int32)]
@@ -216,6 +249,15 @@ _SIGS = {
     "gss_acquire": (C.c_int, [_P, C.POINTER(Acq), _P, _P, _P, C.POINTER(C.c_int)]),
     "gss_acq_expect": (C.c_int, [_P, C.c_double, C.c_int64, C.POINTER(_Truth)]),
     "gss_acq_threshold": (C.c_double, [C.c_int, C.c_uint64, C.c_double]),
+    "gss_trk_defaults": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(Trk)]),
+    "gss_trk_job_from_peak": (C.c_int, [C.POINTER(Acq), _P, C.c_int64, C.c_int32, _P]),
+    "gss_track_host": (C.c_int, [C.POINTER(Trk), _P, C.c_int64, _P, C.c_int, _P, C.c_int64, _P,
+                                 C.c_int]),
+    "gss_track_device": (C.c_int, [_P, C.POINTER(Trk), _P, C.c_int64, _P, C.c_int, _P, C.c_int64,
+                                   _P, _P]),
+    "gss_track": (C.c_int, [_P, C.POINTER(Trk), _P, C.c_int64, _P, C.c_int, _P, C.c_int64, _P]),
+    "gss_nav_decode": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int, C.POINTER(C.c_int32)]),
+    "gss_trk_cn0": (C.c_double, [_P, C.c_int64, C.c_int64]),
     "gss_dev_timing": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float),
                                  C.POINTER(C.c_float)]),
     "gss_dev_timing_lin": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
@@ -405,6 +447,57 @@ def cn0_dbhz(peak, coh_ms=1):
     -inf for a peak not above its floor"""
     r = acq_ratio(peak)
     return float(10 * np.log10((r - 1) / (coh_ms * 1e-3))) if r > 1 else float("-inf")
+
+
+def trk_jobs(acq, peaks, sample0, n_epoch):
+    """TRK_JOB_DTYPE [len(peaks)]: the jobs that continue the peaks of a search that began at
+    sample sample0 (gss_trk_job_from_peak)"""
+    peaks = np.ascontiguousarray(peaks, ACQ_PEAK_DTYPE).reshape(-1)
+    jobs = np.zeros(len(peaks), TRK_JOB_DTYPE)
+    for i in range(len(peaks)):
+        _check(lib().gss_trk_job_from_peak(C.byref(acq), _ptr(peaks[i:i + 1]), int(sample0),
+                                           int(n_epoch), _ptr(jobs[i:i + 1])))
+    return jobs
+
+
+def _trk_args(trk, samples, n, jobs, pitch):
+    x = np.ascontiguousarray(samples)
+    cap = {FMT_SC16: x.nbytes // 4, FMT_SC08: x.nbytes // 2, FMT_SC01: x.nbytes * 4}.get(trk.fmt, 0)
+    n = cap if n is None else int(n)
+    if n > cap:
+        raise ValueError(f"{n} samples asked for, the array holds {cap}")
+    jobs = np.ascontiguousarray(jobs, TRK_JOB_DTYPE).reshape(-1)
+    if pitch is None:
+        pitch = max(int(jobs["n_epoch"].max()), 0) if len(jobs) else 0
+    return x, n, jobs, int(pitch)
+
+
+def track_host(trk, samples, jobs, n=None, pitch=None, threads=8):
+    """Tracking on the host (gss_track_host) over samples (any array holding the format's bytes;
+    n: how many of them, default all): (rec TRK_REC_DTYPE [n_job, pitch], count int32 [n_job])"""
+    x, n, jobs, pitch = _trk_args(trk, samples, n, jobs, pitch)
+    rec = np.zeros((len(jobs), pitch), TRK_REC_DTYPE)
+    count = np.zeros(len(jobs), np.int32)
+    _check(lib().gss_track_host(C.byref(trk), _ptr(x), n, _ptr(jobs), len(jobs), _ptr(rec), pitch,
+                                _ptr(count), threads))
+    return rec, count
+
+
+def nav_decode(rec, skip=-1, cap=64):
+    """The subframes in one job's records (gss_nav_decode): (NAV_SF_DTYPE [found], bit offset)"""
+    rec = np.ascontiguousarray(rec, TRK_REC_DTYPE).reshape(-1)
+    sf = np.zeros(cap, NAV_SF_DTYPE)
+    off = C.c_int32(0)
+    n = lib().gss_nav_decode(_ptr(rec), len(rec), int(skip), _ptr(sf), cap, C.byref(off))
+    if n < 0:
+        _check(n)
+    return sf[:n].copy(), off.value
+
+
+def trk_cn0(rec, skip=500):
+    """tracked C/N0 [dB-Hz] of one job's records from epoch skip on (gss_trk_cn0)"""
+    rec = np.ascontiguousarray(rec, TRK_REC_DTYPE).reshape(-1)
+    return float(lib().gss_trk_cn0(_ptr(rec), len(rec), int(skip)))
 
 
 def lut():
@@ -897,6 +990,24 @@ class Device:
         _check(lib().gss_acquire(self._h, C.byref(acq), _ptr(x), _ptr(peaks), _ptr(grid),
                                  C.byref(sh)))
         return peaks, grid, sh.value
+
+    def track(self, trk, samples_ptr, n, jobs, rec_ptr, pitch, count_ptr, stream=0):
+        """gss_track_device: tracking over the n samples at device pointer samples_ptr; jobs a
+        host TRK_JOB_DTYPE array, records [n_job, pitch] to rec_ptr and the epochs written per
+        job to count_ptr (device pointers).  Asynchronous on stream."""
+        jobs = np.ascontiguousarray(jobs, TRK_JOB_DTYPE).reshape(-1)
+        _check(lib().gss_track_device(self._h, C.byref(trk), C.c_void_p(samples_ptr), int(n),
+                                      _ptr(jobs), len(jobs), C.c_void_p(rec_ptr), int(pitch),
+                                      C.c_void_p(count_ptr), C.c_void_p(stream)))
+
+    def track_from_host(self, trk, samples, jobs, n=None, pitch=None):
+        """gss_track: track() on host samples; returns what track_host() returns."""
+        x, n, jobs, pitch = _trk_args(trk, samples, n, jobs, pitch)
+        rec = np.zeros((len(jobs), pitch), TRK_REC_DTYPE)
+        count = np.zeros(len(jobs), np.int32)
+        _check(lib().gss_track(self._h, C.byref(trk), _ptr(x), n, _ptr(jobs), len(jobs),
+                               _ptr(rec), pitch, _ptr(count)))
+        return rec, count
 
     def run(self, scn, sink, first_block=0, n_blocks=-1, batch=100, threads=8, impair=None):
         """Stream blocks [first_block, first_block + n_blocks) of Scenario scn through gss_run;

@@ -303,6 +303,97 @@ int gss_acq_expect(const gss_chan_blk_t *row, double fs, int64_t sample_in_block
    with probability about pfa).  NaN on bad arguments.                                         */
 double gss_acq_threshold(int M, uint64_t cells, double pfa);
 
+/* ---- signal tracking and LNAV decoding ----------------------------------------------------------
+   What a receiver does after the search (an extension): per job one satellite's
+   code and carrier are tracked over the samples, one record per code period, and the records'
+   prompt sums are demodulated into navigation subframes.  The loops are an exact integer machine
+   (csrc/common/gss_trk.h); host, device and tests/trk_oracle.py agree bit for bit on every record.
+     constants  M = 1023 2^32 (code phase in 2^-32 chip), cs_nom = floor((1023000 2^32 + fs / 2) /
+                fs); tables cos512 / sin512 of gss_lut; chips of row prn - 1 of gss_ca_table
+     state      sample s = s0, code phase phi = 0, carrier phase th = 0 (uint32), carrier step
+                w = w0 (int32, 2^-32 cycle per sample), W = w0 2^16 (int64), code step
+                cs = cs_nom + w0 / 1540 (C's truncating division)
+     epoch e    n = ceil((M - phi) / cs) samples; the job ends after n_epoch epochs or at the first
+                epoch with s + n > N.  Sample i < n: c = phi + i cs; chips at c >> 32 (prompt),
+                ((c + 2^31) mod M) >> 32 (early), ((c - 2^31) mod M) >> 32 (late), set -> +1, clear
+                -> -1; carrier index ((th + i w) mod 2^32) >> 23; yI = xI cos + xQ sin, yQ = xQ cos
+                - xI sin; IE, QE, IP, QP, IL, QL = sum y chip (int64)
+     discrim.   amb(a, b) = max(|a|, |b|) + (min(|a|, |b|) >> 1); m = amb(IP, QP); u = IP 2^14 / m,
+                v = QP 2^14 / m (truncating; 0 when m == 0); D_pll = u < 0 ? -v : v; D_fll = 0 in
+                the job's first epoch, else with (u', v') of the epoch before cross = u' v - v' u,
+                dot = u' u + v' v, D_fll = (dot < 0 ? -cross : cross) >> 14 (every >> floors);
+                D_dll = (mE - mL) 2^14 / (mE + mL), mE = amb(IE, QE), mL = amb(IL, QL), 0 for 0 / 0
+     update     th += n w; phi += n cs - M; s += n; e < n_pull: W += Kf D_fll, w = W >> 16; else
+                W += Ki D_pll, w = (W + Kp D_pll) >> 16; W wraps mod 2^64 and w keeps the low 32
+                bits; cs = cs_nom + w / 1540 + ((Kd D_dll) >> 16)                               */
+typedef struct gss_trk_cfg {
+    int32_t fs_hz;               /* sample rate [Hz]                                            */
+    int32_t fmt;                 /* GSS_FMT_SC16 / SC08 / SC01                                  */
+    int32_t n_pull;              /* epochs of the frequency-locked pull-in, >= 0                */
+    int32_t Kf, Ki, Kp, Kd;      /* loop gains, 0..2^30                                         */
+} gss_trk_cfg_t;
+typedef struct gss_trk_job {
+    int64_t s0;                  /* sample where a code period starts, >= 0                     */
+    int32_t prn;                 /* 1..32                                                       */
+    int32_t w0;                  /* carrier step at the start [2^-32 cycle per sample]          */
+    int32_t n_epoch;             /* epochs to track, 0..pitch                                   */
+    int32_t pad;
+} gss_trk_job_t;                 /* 24 bytes                                                    */
+typedef struct gss_trk_rec {
+    int64_t IE, QE, IP, QP, IL, QL;
+    int64_t s;                   /* the epoch's first sample                                    */
+    int32_t w;                   /* the carrier step the epoch used                             */
+    int32_t dcs;                 /* the code step it used, minus cs_nom                         */
+} gss_trk_rec_t;                 /* 64 bytes                                                    */
+typedef struct gss_nav_sf {      /* one decoded subframe                                        */
+    int64_t  sample;             /* first sample of its first epoch                             */
+    int32_t  epoch;              /* index of that epoch's record                                */
+    int32_t  polarity;           /* 1: the prompt sums were inverted                            */
+    int32_t  tow, id;            /* TOW count and subframe id of the hand-over word             */
+    uint32_t word[10];           /* the ten 30-bit words as transmitted                         */
+} gss_nav_sf_t;                  /* 64 bytes                                                    */
+
+/* The default loop: n_pull = 300 and, in double with T = 1e-3 and wn = 34 (an 18 Hz loop),
+   Ki = round(wn^2 T 2^34 / (2 pi fs)), Kp = round(1.414 wn 2^34 / (2 pi fs)), Kf = round(0.05
+   2^34 / (2 pi T fs)), Kd = round(8 2^33 / fs).  GSS_E_ARG for a cfg gss_track_* rejects.      */
+int gss_trk_defaults(int32_t fs_hz, int32_t fmt, gss_trk_cfg_t *cfg);
+/* The job that continues a peak of a search that began at sample `sample0`: s0 = sample0 + tau,
+   w0 = the carrier step of the peak's bin.                                                     */
+int gss_trk_job_from_peak(const gss_acq_t *a, const gss_acq_peak_t *peak, int64_t sample0,
+                          int32_t n_epoch, gss_trk_job_t *job);
+/* Tracking on the host (the reference statement): samples = N samples of cfg->fmt, rec
+   [n_job][pitch], count [n_job] = the epochs written per job; jobs spread over threads.
+   GSS_E_ARG for a cfg in which cs could reach 0 or M (cs_nom -+ (2^31 / 1540 + Kd / 4 + 2)), a
+   field out of its range, a PRN outside 1..32, s0 < 0 or n_epoch outside 0..pitch.             */
+int gss_track_host(const gss_trk_cfg_t *cfg, const void *samples, int64_t N,
+                   const gss_trk_job_t *jobs, int n_job, gss_trk_rec_t *rec, int64_t pitch,
+                   int32_t *count, int threads);
+/* The same on the device: d_samples, d_rec (8-byte aligned) and d_count are device pointers,
+   jobs is a host array (read before the call returns); asynchronous on stream.  A launch
+   advances every job by at most 4096 epochs and leaves its state in device scratch (kept per
+   device, grown on first use, synchronously; one call per device may be in flight).
+   GSS_TRK_PATH=plain takes the plain form of the kernel (same records).                        */
+int gss_track_device(gss_dev *d, const gss_trk_cfg_t *cfg, const void *d_samples, int64_t N,
+                     const gss_trk_job_t *jobs, int n_job, gss_trk_rec_t *d_rec, int64_t pitch,
+                     int32_t *d_count, void *stream);
+/* gss_track_device from host buffers: uploads, tracks, downloads, synchronises.                */
+int gss_track(gss_dev *d, const gss_trk_cfg_t *cfg, const void *samples, int64_t N,
+              const gss_trk_job_t *jobs, int n_job, gss_trk_rec_t *rec, int64_t pitch,
+              int32_t *count);
+/* LNAV subframes out of one job's n records.  Bit sync from epoch `skip` (< 0: 500): with nb =
+   (n - skip - 19) / 20 bits per candidate, the offset o in 0..19 (to *bit_offset, may be NULL)
+   that maximises sum_bits |sum_20 IP|, ties to the lowest; a bit is 1 when its 20-epoch sum of
+   IP is >= 0.  Frame sync at every bit position with two bits before it (D29*, D30*), in both
+   polarities: a subframe is accepted when its first eight bits are 10001011 and all ten words
+   pass the IS-GPS-200 parity; the scan goes on behind it.  Returns the number of subframes
+   written to sf[0 .. cap), or GSS_E_ARG.                                                       */
+int gss_nav_decode(const gss_trk_rec_t *rec, int64_t n, int64_t skip, gss_nav_sf_t *sf, int cap,
+                   int32_t *bit_offset);
+/* Tracked C/N0 [dB-Hz] from the prompt powers P = IP^2 + QP^2 of records [skip, n) by their
+   moments M2 = mean P, M4 = mean P^2: Pd = sqrt(2 M2^2 - M4), Pn = M2 - Pd, 10 log10(Pd / Pn /
+   1e-3).  NaN when the moments leave no signal or fewer than two records remain.               */
+double gss_trk_cn0(const gss_trk_rec_t *rec, int64_t n, int64_t skip);
+
 /* Kernel timing from HIP events recorded on the launch stream around every Stage A and Stage B
    launch (gss_synth_device, gss_anchor_device, gss_render_device; rings of the last 256 of
    each).  reset!=0 clears the rings (no sync); otherwise waits for the last launches and
