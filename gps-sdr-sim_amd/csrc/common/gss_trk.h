@@ -17,6 +17,8 @@
 #define GSS_TRK_HALF   (1LL << 31)             /* the early / late offset: half a chip          */
 #define GSS_TRK_KMAX   (1 << 30)               /* the gains' upper limit                        */
 #define GSS_TRK_WSPAN  (2147483648LL / 1540 + 2)   /* |w / 1540| stays below this               */
+#define GSS_TRK_CSMIN  (GSS_TRK_M >> 23)       /* the code step stays above this: n < 2^23      */
+#define GSS_TRK_S0MAX  (1LL << 62)             /* a job's first sample: s + n stays in int64    */
 
 typedef struct gss_trk_state {
     int64_t  s;                  /* next epoch's first sample                                   */
@@ -49,15 +51,17 @@ GSS_ACQ_HD int gss_trk_check(const gss_trk_cfg_t *c, const char **why)
         c->Kp < 0 || c->Kp > GSS_TRK_KMAX || c->Kd < 0 || c->Kd > GSS_TRK_KMAX) {
         *why = "a gain outside 0..2^30"; return -1;
     }
-    /* |w / 1540| < WSPAN for every int32 w, |(Kd D_dll) >> 16| <= Kd / 4 + 1 as |D_dll| <= 2^14 */
+    /* |w / 1540| < WSPAN for every int32 w, |(Kd D_dll) >> 16| <= Kd / 4 + 1 as |D_dll| <= 2^14;
+       a code step above M / 2^23 keeps every epoch shorter than 2^23 samples */
     const int64_t span = GSS_TRK_WSPAN + c->Kd / 4 + 2, cn = gss_trk_cs_nom(c->fs_hz);
-    if (cn - span <= 0 || cn + span >= GSS_TRK_M) {
-        *why = "the code step could reach 0 or a whole code period"; return -1;
+    if (cn - span <= GSS_TRK_CSMIN || cn + span >= GSS_TRK_M) {
+        *why = "the code step could reach M / 2^23 or a whole code period"; return -1;
     }
     return 0;
 }
 
-/* samples of the epoch that starts at code phase phi: ceil((M - phi) / cs) */
+/* samples of the epoch that starts at code phase phi: ceil((M - phi) / cs), below 2^23 for every
+   code step gss_trk_check admits */
 GSS_ACQ_HD int32_t gss_trk_len(int64_t phi, int64_t cs)
 {
     return (int32_t)((GSS_TRK_M - phi + cs - 1) / cs);

@@ -162,8 +162,11 @@ __global__ __launch_bounds__(NT) void gss_track_kernel(TrkArgs A)
         gss_trk_init(&t, &jb, A.cs_nom);
     else
         t = A.state[job];
-    if (t.done || t.e >= jb.n_epoch)                 /* uniform over the workgroup              */
+    if (t.done || t.e >= jb.n_epoch) {               /* uniform over the workgroup              */
+        if (A.first && tid == 0)                     /* n_epoch 0: a later launch reads this    */
+            A.state[job] = t;
         return;
+    }
     load_tables(tab, A, jb.prn, NT);
     __syncthreads();
     gss_trk_rec_t *rec = A.rec + (size_t)job * A.pitch;

@@ -23,8 +23,11 @@ int gss_trk_check_args(const gss_trk_cfg_t *cfg, int64_t N, const gss_trk_job_t 
     for (int j = 0; j < n_job; j++) {
         if (jobs[j].prn < 1 || jobs[j].prn > 32)
             return gss_fail(GSS_E_ARG, "tracking job %d: PRN %d outside 1..32", j, jobs[j].prn);
-        if (jobs[j].s0 < 0 || jobs[j].n_epoch < 0 || jobs[j].n_epoch > pitch)
-            return gss_fail(GSS_E_ARG, "tracking job %d: s0 below 0 or n_epoch outside 0..pitch", j);
+        /* s0 + an epoch + the samples the kernel loads ahead must not leave int64 */
+        if (jobs[j].s0 < 0 || jobs[j].s0 > GSS_TRK_S0MAX || jobs[j].n_epoch < 0 ||
+            jobs[j].n_epoch > pitch)
+            return gss_fail(GSS_E_ARG,
+                            "tracking job %d: s0 outside 0..2^62 or n_epoch outside 0..pitch", j);
     }
     return 0;
 }

@@ -325,7 +325,11 @@ double gss_acq_threshold(int M, uint64_t cells, double pfa);
                 D_dll = (mE - mL) 2^14 / (mE + mL), mE = amb(IE, QE), mL = amb(IL, QL), 0 for 0 / 0
      update     th += n w; phi += n cs - M; s += n; e < n_pull: W += Kf D_fll, w = W >> 16; else
                 W += Ki D_pll, w = (W + Kp D_pll) >> 16; W wraps mod 2^64 and w keeps the low 32
-                bits; cs = cs_nom + w / 1540 + ((Kd D_dll) >> 16)                               */
+                bits; cs = cs_nom + w / 1540 + ((Kd D_dll) >> 16)
+     limits     |w / 1540| <= 2^31 / 1540 and |(Kd D_dll) >> 16| <= Kd / 4 + 1 (|D_dll| <= 2^14), so
+                with span = 2^31 / 1540 + Kd / 4 + 4 every cs lies inside cs_nom -+ span.  The calls
+                reject a cfg with cs_nom - span <= M >> 23 (523,776) or cs_nom + span >= M: an
+                epoch is then 1 <= n < 2^23 samples and no intermediate leaves int64            */
 typedef struct gss_trk_cfg {
     int32_t fs_hz;               /* sample rate [Hz]                                            */
     int32_t fmt;                 /* GSS_FMT_SC16 / SC08 / SC01                                  */
@@ -333,7 +337,7 @@ typedef struct gss_trk_cfg {
     int32_t Kf, Ki, Kp, Kd;      /* loop gains, 0..2^30                                         */
 } gss_trk_cfg_t;
 typedef struct gss_trk_job {
-    int64_t s0;                  /* sample where a code period starts, >= 0                     */
+    int64_t s0;                  /* sample where a code period starts, 0..2^62                  */
     int32_t prn;                 /* 1..32                                                       */
     int32_t w0;                  /* carrier step at the start [2^-32 cycle per sample]          */
     int32_t n_epoch;             /* epochs to track, 0..pitch                                   */
@@ -363,8 +367,9 @@ int gss_trk_job_from_peak(const gss_acq_t *a, const gss_acq_peak_t *peak, int64_
                           int32_t n_epoch, gss_trk_job_t *job);
 /* Tracking on the host (the reference statement): samples = N samples of cfg->fmt, rec
    [n_job][pitch], count [n_job] = the epochs written per job; jobs spread over threads.
-   GSS_E_ARG for a cfg in which cs could reach 0 or M (cs_nom -+ (2^31 / 1540 + Kd / 4 + 2)), a
-   field out of its range, a PRN outside 1..32, s0 < 0 or n_epoch outside 0..pitch.             */
+   GSS_E_ARG for a cfg in which cs could fall to M / 2^23 (523,776: an epoch of 2^23 samples) or
+   reach M (cs_nom -+ (2^31 / 1540 + Kd / 4 + 4)), a field out of its range, a PRN outside 1..32,
+   s0 outside 0..2^62 or n_epoch outside 0..pitch.                                              */
 int gss_track_host(const gss_trk_cfg_t *cfg, const void *samples, int64_t N,
                    const gss_trk_job_t *jobs, int n_job, gss_trk_rec_t *rec, int64_t pitch,
                    int32_t *count, int threads);

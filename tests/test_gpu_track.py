@@ -1,6 +1,9 @@
 """Signal tracking on the GPU (csrc/hip/gss_track.hip): Device.track against the numpy restatement
-of tests/trk_oracle.py, bit for bit, on both forms of the kernel; more jobs than CUs; the state
-hand-over between launches; the scratch regrowing; and end to end: a noisy run of the synthesiser
+of tests/trk_oracle.py, bit for bit, on both forms of the kernel, on its shapes and on its input
+families (epochs of 1 to 135,000 samples on every edge of the fast form's sample loop, saturating
+input, the feedback at the ends of its arguments, jobs that end where the samples do); more jobs
+than CUs; the state hand-over between launches, also past jobs of no epochs; the scratch
+regrowing; and end to end: a noisy run of the synthesiser
 is tracked on the device for 12.4 s, and the subframes read back are its nav rows' words at the
 samples its channel rows say."""
 import subprocess
@@ -78,6 +81,51 @@ def test_device_equals_oracle(dev, monkeypatch, si, fmt, path):
     O.same_records(rec, count, wrec, wcount)
 
 
+def device_equals(dev, c, in_off=0):
+    rec, count = on_device(dev, O.trk_of(c["fs"], c["fmt"], c["gains"]), c["data"], c["N"],
+                           O.jobs_array(c["jobs"]), c["pitch"], in_off=in_off)
+    O.same_records(rec, count, c["rec"], c["count"])
+
+
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name", O.RATES)
+def test_device_at_every_length(dev, monkeypatch, name, path):
+    """epochs of 1 to 135,000 samples: each edge of the fast form's sample loop (the samples
+    loaded ahead, the passes of four behind them, the flush of the int32 sums)"""
+    c = O.case(name)
+    set_path(monkeypatch, path)
+    device_equals(dev, c, in_off=2 if c["fmt"] == 16 else 1)
+
+
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name", O.SATURATING)
+def test_device_saturating(dev, monkeypatch, name, path):
+    """a lane's prompt sum passes 2^31 within the epoch: wrong without the flush into int64"""
+    set_path(monkeypatch, path)
+    device_equals(dev, O.case(name))
+
+
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name", O.FEEDBACK + O.ENDS)
+def test_device_feedback_and_ends(dev, monkeypatch, name, path):
+    set_path(monkeypatch, path)
+    device_equals(dev, O.case(name))
+
+
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("chunk", [1, 7, 40])
+def test_hand_over_with_jobs_that_end_early(dev, monkeypatch, chunk, path):
+    """Launches of 1, 7 and all 40 epochs over jobs of 0, 1 and 40 epochs, one of which ends
+    one sample short of its 40th and one runs out of samples in its eleventh (the second launch
+    of 7).  Jobs finish in different launches; the job of no epochs, whose state only the first
+    launch can write, keeps count 0 and untouched records through every later one."""
+    c = O.case("ends_64000_short")
+    assert list(c["count"]) == [39, 0, 0, 0, 0, 1, 10] and c["jobs"][4][3] == 0
+    assert max(j[3] for j in c["jobs"]) == 40
+    set_path(monkeypatch, path, chunk=chunk)
+    device_equals(dev, c)
+
+
 @pytest.mark.parametrize("path", PATHS)
 def test_state_hand_over_between_launches(dev, monkeypatch, path):
     """60 epochs in launches of 16: the state written back by one launch continues the next"""
@@ -139,6 +187,8 @@ def test_device_argument_errors(dev):
     for trk, jobs, x, r, c, pitch in [
             (ok, O.jobs_array([(33, 0, 0, 4)]), p, p + 4096, p + 8192, 4),
             (ok, O.jobs_array([(1, -5, 0, 4)]), p, p + 4096, p + 8192, 4),
+            (ok, O.jobs_array([(1, 2**63 - 1, 0, 4)]), p, p + 4096, p + 8192, 4),
+            (ok, O.jobs_array([(1, 2**62 + 1, 0, 4)]), p, p + 4096, p + 8192, 4),
             (ok, okj, p, p + 4096, p + 8192, 3),
             (low, okj, p, p + 4096, p + 8192, 4),
             (G.Trk(64000, 16, Ki=-1), okj, p, p + 4096, p + 8192, 4),
@@ -148,6 +198,21 @@ def test_device_argument_errors(dev):
         with pytest.raises(G.GssError) as e:
             dev.track(trk, x, 1000, jobs, r, pitch, c)
         assert e.value.code == -1
+    # A code step that could fall to M >> 23 (an epoch of 2^23 samples and more) is refused by
+    # the argument check, which runs before any launch; just inside the bound the call runs,
+    # and the one epoch, longer than the samples, does not.
+    far = O.jobs_array([(1, 0, -2**31, 4)])
+    fs, inside, outside = O.longest_cfg()
+    x8 = O.random_samples(1000, 8, 2)
+    for trk in (G.Trk(fs, 8, n_pull=0, Kf=0, Ki=0, Kp=0, Kd=3209600), O.trk_of(fs, 8, outside)):
+        with pytest.raises(G.GssError) as e:
+            dev.track(trk, p, 1000, far, p + 4096, 4, p + 8192)
+        assert e.value.code == -1
+        with pytest.raises(G.GssError) as e:
+            dev.track_from_host(trk, x8, far)
+        assert e.value.code == -1
+    rec, count = on_device(dev, O.trk_of(fs, 8, inside), x8, 1000, far, 4)
+    assert count[0] == 0
     torch.cuda.synchronize()
 
 

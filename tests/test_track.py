@@ -1,6 +1,9 @@
 """Signal tracking and LNAV decoding on the host (csrc/host/track.c, navdec.c):
 gss_track_host against the numpy restatement of tests/trk_oracle.py, bit for bit, on random
-samples where the loops never lock; the default gains and the argument limits; the decoder on
+samples where the loops never lock, and on the input families of trk_oracle.py (every epoch
+length at which the kernel takes another path, saturating input, the feedback at the ends of its
+arguments, jobs that end where the samples do, the longest epoch the limits admit), with the
+assertions that those inputs reach what they are for; the default gains and the argument limits; the decoder on
 synthetic record streams; and the physical test: the static scenario's satellites are tracked
 for 12.4 s through noise, and the subframes read back are the nav rows' words at the samples the
 channel rows say."""
@@ -24,6 +27,118 @@ def test_host_equals_oracle(si, fmt):
     rec, count = G.track_host(O.trk_of(fs, fmt, O.gains_of(fs, n_pull)), data,
                               O.jobs_array(jobs), n=N, threads=2)
     O.same_records(rec, count, wrec, wcount)
+
+
+def host_equals(c):
+    rec, count = G.track_host(O.trk_of(c["fs"], c["fmt"], c["gains"]), c["data"],
+                              O.jobs_array(c["jobs"]), n=c["N"], pitch=c["pitch"], threads=2)
+    O.same_records(rec, count, c["rec"], c["count"])
+    for j, n in enumerate(count):                            # rec starts zeroed
+        assert not rec[j, n:].view(np.uint8).any(), j
+
+
+@pytest.mark.parametrize("name", O.RATES)
+def test_host_at_every_length(name):
+    c = O.case(name)
+    assert c["count"][0] == c["jobs"][0][3] and c["count"][1] == c["jobs"][1][3]
+    assert 0 < c["count"][2] < c["jobs"][2][3]
+    assert c["gains"][0] < c["count"][0]
+    host_equals(c)
+
+
+def seen(fs_list):
+    """the epoch lengths that some job of the RATES rows of these rates runs"""
+    out = set()
+    for fs in fs_list:
+        for fmt in (16, 8, 1):
+            c = O.case(f"rate_{fs}_sc{fmt:02d}")
+            for j in range(len(c["jobs"])):
+                out |= set(int(n) for n in O.lengths(c, j))
+    return out
+
+
+def test_the_rates_reach_the_edges():
+    """the lengths that matter, so that a change of the kernel's constants cannot move its
+    edges away from the tests without this failing"""
+    assert seen([1001]) == {1, 2}
+    assert seen([2046]) == {2, 3}
+    assert {63, 64} <= seen([63000]) and {64, 65} <= seen([65000])
+    assert {511, 512} <= seen([511000]) and {511, 512, 513} <= seen([512000])
+    assert 513 in seen([513000])
+    assert {1023, 1024} <= seen([1023000])
+    assert {O.AHEAD - 1, O.AHEAD} <= seen([3071000])
+    assert {O.AHEAD - 1, O.AHEAD, O.AHEAD + 1} <= seen([3072000])
+    assert {O.AHEAD + 1, O.AHEAD + 2} <= seen([3073000])
+    # at AHEAD + 512 the next sample lands on a pass's second slot, one more and it is live
+    assert {O.AHEAD + 511, O.AHEAD + 512, O.AHEAD + 513} <= seen([3584000])
+    # the first pass of four samples a lane ends at AHEAD + 2048
+    assert {O.AHEAD + 2048, O.AHEAD + 2049} <= seen([5120000])
+    assert {O.AHEAD + 2048, O.AHEAD + 2049, O.AHEAD + 2050} <= seen([5121000])
+    assert {O.FIRST_FLUSH, O.FIRST_FLUSH + 1} <= seen([64512000])
+    for fs in (64512000, 64513000, 130000000):
+        assert max(seen([fs])) > O.FIRST_FLUSH
+    assert min(seen([130000000])) > 2 * O.FIRST_FLUSH
+
+
+@pytest.mark.parametrize("name", O.SATURATING)
+def test_host_saturating(name):
+    c = O.case(name)
+    assert c["count"][0] == 3
+    sums, ymax = O.lane_sums(c)
+    print(name, "largest lane sum", np.abs(sums).max(), "= 2^31 x", np.abs(sums).max() / 2**31,
+          "max |y|", ymax)
+    # an int32 partial sum that is never flushed overflows
+    assert (sums < -2**31).any() if name.endswith("inverted") else (sums >= 2**31).any()
+    host_equals(c)
+
+
+@pytest.mark.parametrize("name", O.FEEDBACK)
+def test_host_feedback(name):
+    c = O.case(name)
+    kind = name.rsplit("_", 1)[1]
+    assert (c["count"] > 10).all()
+    if kind == "pullall":
+        assert c["gains"][0] > max(j[3] for j in c["jobs"])
+    if kind == "wrap":                                       # w changes sign by wrapping
+        w = c["rec"]["w"].astype(np.int64)
+        assert any((np.abs(np.diff(w[j, :n])) > 2**31).any() for j, n in enumerate(c["count"]))
+    if kind == "maxkd":                                      # the length hint falls back
+        assert max(np.abs(np.diff(O.lengths(c, j))).max() for j in range(3)) > 1
+    if kind == "zeros":
+        # every discriminator takes its 0 / 0 branch
+        assert not c["rec"]["IP"].any() and not c["rec"]["IL"].any()
+        assert all((c["rec"]["w"][j] == job[2]).all() for j, job in enumerate(c["jobs"]))
+    host_equals(c)
+
+
+@pytest.mark.parametrize("name", O.ENDS)
+def test_host_ends(name):
+    c = O.case(name)
+    kind = name.split("_", 2)[2]
+    if kind in ("exact", "short"):
+        assert list(c["count"]) == [40 if kind == "exact" else 39, 0, 0, 0, 0, 1, 10]
+        end = c["rec"]["s"][0, 39] if kind == "short" else None
+        assert end is None or end < c["N"]
+    else:
+        k = int(kind[-1])
+        assert c["N"] % 4 == (O.case(name[:-1] + "0")["N"] - k) % 4
+        assert sorted(j[1] % 4 for j in c["jobs"]) == [0, 1, 2, 3]
+        assert c["count"][0] == (40 if k == 0 else 39) and (c["count"] >= 38).all()
+    assert c["pitch"] > max(j[3] for j in c["jobs"])
+    host_equals(c)
+
+
+def test_host_longest_epoch():
+    """2 GS/s, w0 = -2^31, the largest Kd the limits admit and an input that drives the code
+    step to its floor: the second epoch is nearly 2^23 samples, and its length stays an int32"""
+    c = O.case(O.LONGEST)
+    assert c["count"][0] == 2
+    cs1 = O.cs_nominal(c["fs"]) + int(c["rec"]["dcs"][0, 1])
+    n1 = -(-(O.M - (int(O.lengths(c, 0)[0]) * (O.cs_nominal(c["fs"]) + int(c["rec"]["dcs"][0, 0]))
+                   - O.M)) // cs1)
+    print("code step", cs1, "floor", O.CS_MIN + 1, "epoch", n1, "of 2^23 =", 2**23)
+    assert O.CS_MIN < cs1 < O.CS_MIN + 1200 and 8370000 < n1 < 2**23
+    host_equals(c)
 
 
 def test_default_gains():
@@ -61,6 +176,11 @@ def test_argument_limits():
         bad(G.Trk(fs, 16), O.jobs_array([(prn, 0, 0, 4)]))
     bad(G.Trk(fs, 16), O.jobs_array([(1, -1, 0, 4)]))
     bad(G.Trk(fs, 16), O.jobs_array([(1, 0, 0, -1)]))
+    # s0 so large that s0 + an epoch would leave int64 (the sum used to wrap to a sample in
+    # front of the buffer); 2^62 itself is far behind N: no epoch
+    bad(G.Trk(fs, 16), O.jobs_array([(1, 2**63 - 1, 0, 4)]))
+    bad(G.Trk(fs, 16), O.jobs_array([(1, 2**62 + 1, 0, 4)]))
+    assert G.track_host(G.Trk(fs, 16), x, O.jobs_array([(1, 2**62, 0, 4)]))[1][0] == 0
     bad(G.Trk(fs, 16), ok, pitch=3)                          # n_epoch above pitch
     bad(G.Trk(fs, 16, Kd=-1), ok)
     bad(G.Trk(fs, 16, Kp=2**30 + 1), ok)
@@ -77,6 +197,26 @@ def test_argument_limits():
     t = G.Trk(2000000000, 16)                                # cs_nom 2.2e6 > span 1.39e6: accepted
     t.Kd = 2**30                                             # span + Kd / 4 > cs_nom
     bad(t, ok)
+    # The code step could fall to M >> 23, an epoch reach 2^23 samples.  Kd = 3,209,600 leaves
+    # cs_nom - span = 3: with w0 = -2^31 and an input that empties the early correlator the
+    # second epoch would need 2.8e9 samples, more than its int32 length holds.  Rejected before
+    # anything runs (and never to be run un-rejected).
+    kw = dict(n_pull=0, Kf=0, Ki=0, Kp=0)
+    far = O.jobs_array([(1, 0, -2**31, 4)])
+    x8 = O.random_samples(1000, 8, 2)
+    assert O.cs_nominal(2000000000) - (O.WSPAN + 3209600 // 4 + 2) == 3
+    with pytest.raises(G.GssError) as e:
+        G.track_host(G.Trk(2000000000, 8, Kd=3209600, **kw), x8, far)
+    assert e.value.code == -1 and "2^23" in str(e.value)
+    fs, inside, outside = O.longest_cfg()
+    with pytest.raises(G.GssError) as e:
+        G.track_host(O.trk_of(fs, 8, outside), x8, far)
+    assert e.value.code == -1
+    rec, count = G.track_host(O.trk_of(fs, 8, inside), x8, far)   # accepted: no epoch fits
+    assert count[0] == 0
+    for f in (16, 8, 1):                                      # what the suite tracks stays accepted
+        for r in [s[0] for s in O.SHAPES] + [r for r, _ in O.RATE_TABLE] + [1000000, 2000000000]:
+            G.track_host(G.Trk(r, f), x, O.jobs_array([(1, 10**6, 0, 1)]))
     # SC16 samples at an odd address
     raw = np.zeros(4001, np.uint8)
     with pytest.raises(G.GssError):

@@ -169,6 +169,206 @@ def same_records(rec, count, wrec, wcount):
         assert len(bad) == 0, (j, bad[:4], rec[j, bad[:1]], wrec[j, bad[:1]])
 
 
+# ---- input families --------------------------------------------------------------------------
+# Synthetic inputs that reach what the shapes above do not: every epoch length at which the fast
+# form of the kernel takes another path, the int32 partial sums at their limit, the feedback at
+# the ends of its arguments, and jobs that end exactly where the samples do.  A case is a dict
+# (fs, fmt, N, gains, jobs, pitch, data, rec, count), built with the oracle's answer on first use
+# (case(name)) and kept; the names are static, so a test module lists them without building any.
+AHEAD = 3072            # gss_track.hip: samples of an epoch the fast form loads ahead
+FIRST_FLUSH = 64512     # AHEAD + 30 passes of 2048: beyond it the int32 sums flush into int64
+WSPAN = 2**31 // 1540 + 2
+CS_MIN = M >> 23        # gss_trk_check: the code step stays above this, so an epoch is < 2^23
+
+# (fs, epochs): the lengths 1..3, the wave and workgroup edges, one sample a chip, the end of the
+# samples loaded ahead, the first lane that takes a second sample of a four-sample pass (3,584:
+# below it only the pass's first sample is live, so its later masks and phase steps do not
+# show), the end of the first pass, the first flush, and 130 MS/s
+RATE_TABLE = ((1001, 40), (2046, 40), (63000, 12), (65000, 12), (511000, 12), (512000, 12),
+              (513000, 12), (1023000, 12), (3071000, 10), (3072000, 10), (3073000, 10),
+              (3584000, 10), (5120000, 8), (5121000, 8), (64512000, 6), (64513000, 6),
+              (130000000, 5))
+RATES = [f"rate_{fs}_sc{fmt:02d}" for fs, _ in RATE_TABLE for fmt in (16, 8, 1)]
+SATURATING = ["saturating", "saturating_inverted"]
+FEEDBACK_FS = (64000, 3073000)
+FEEDBACK = [f"feedback_{fs}_{k}" for fs in FEEDBACK_FS
+            for k in ("pull0", "pullall", "nogain", "wrap", "maxkd", "zeros", "negfull")]
+ENDS_FS = (64000, 5121000)
+ENDS = [f"ends_{fs}_{k}" for fs in ENDS_FS
+        for k in ("exact", "short", "sc01_n0", "sc01_n1", "sc01_n2", "sc01_n3")]
+LONGEST = "longest_epoch"
+
+
+def kd_max(fs):
+    """the largest Kd gss_trk_check admits at fs"""
+    cn = cs_nominal(fs)
+    return min(2**30, 4 * (cn - WSPAN - 2 - CS_MIN - 1) + 3, 4 * (M - cn - WSPAN - 2 - 1) + 3)
+
+
+def chips_of(prn):
+    """the +-1 chips of a PRN, int64 [1023]"""
+    row = G.ca_table()[prn - 1]
+    k = np.arange(1023)
+    return 2 * ((row[k >> 5] >> (k & 31).astype(np.uint32)) & 1).astype(np.int64) - 1
+
+
+def pack(xi, xq, fmt):
+    """the bytes of samples (xI, xQ) in a format (SC01: +1 is a set bit, MSB first)"""
+    v = np.empty(2 * len(xi), np.int64)
+    v[0::2], v[1::2] = xi, xq
+    if fmt == 16:
+        return v.astype("<i2").view(np.uint8)
+    if fmt == 8:
+        return v.astype(np.int8).view(np.uint8)
+    return np.packbits((v > 0).astype(np.uint8))
+
+
+def lengths(c, j):
+    """the lengths of job j's epochs but the last, from the records' first samples"""
+    return np.diff(c["rec"]["s"][j, :c["count"][j]])
+
+
+def _finish(fs, fmt, N, gains, jobs, data, pitch=None):
+    pitch = pitch or max(max(j[3] for j in jobs), 1)
+    rec, count = track(data, fmt, N, fs, gains, jobs, pitch)
+    return dict(fs=fs, fmt=fmt, N=N, gains=gains, jobs=jobs, pitch=pitch, data=data, rec=rec,
+                count=count)
+
+
+def _rate(fs, ne, fmt):
+    """three jobs as in shapes(): w0 of +1234 Hz, -2750 Hz and -2^31; the last starts so late
+    that it runs out of samples inside an epoch; n_pull = 3 lies inside the run"""
+    T = -(-fs // 1000)
+    N = ne * fs // 1000 + T // 2 + 7
+    jobs = [(1, 3, _w(1234, fs), ne), (17, T // 2 + 1, _w(-2750, fs), ne - ne // 4),
+            (32, N - (3 * ne + 2) * fs // 6000, -2**31, ne)]
+    return _finish(fs, fmt, N, gains_of(fs, 3), jobs, random_samples(N, fmt, fs % 9973 + fmt))
+
+
+def _saturating(inverted):
+    """Every product of the prompt correlator at its largest, all of one sign: xI = 32767 where
+    cos * chip >= 0, else -32768, xQ likewise with sin.  With all gains 0 the phases are those
+    of the start, so the samples can be written down; one lane of the kernel (every 512th sample
+    of an epoch) sums past 2^31."""
+    fs, prn = 130000000, 5
+    w0 = _w(1234567, fs)
+    cs = cs_nominal(fs) + tdiv(w0, 1540)
+    N = -(-3 * M // cs) + 5
+    i = np.arange(N, dtype=np.int64)
+    p = chips_of(prn)[((i * cs) % M) >> 32]
+    sin512, cos512 = (t.astype(np.int64) for t in G.lut())
+    idx = ((i * w0) % 2**32) >> 23
+    xi = np.where((cos512[idx] * p >= 0) != inverted, 32767, -32768)
+    xq = np.where((sin512[idx] * p >= 0) != inverted, 32767, -32768)
+    return _finish(fs, 16, N, (0, 0, 0, 0, 0), [(prn, 0, w0, 3)], pack(xi, xq, 16))
+
+
+def lane_sums(c, lanes=512):
+    """the prompt I sums of epoch 0 of job 0 as the fast form's lanes hold them: int64 [lanes]"""
+    prn, s0, w0, _ = c["jobs"][0]
+    n = int(lengths(c, 0)[0])
+    cs = cs_nominal(c["fs"]) + tdiv(w0, 1540)
+    xi, xq = unpack(c["data"], c["fmt"], c["N"])
+    i = np.arange(n, dtype=np.int64)
+    sin512, cos512 = (t.astype(np.int64) for t in G.lut())
+    idx = ((i * w0) % 2**32) >> 23
+    y = (xi[s0:s0 + n] * cos512[idx] + xq[s0:s0 + n] * sin512[idx]) * chips_of(prn)[(i * cs) >> 32]
+    return np.bincount(i % lanes, weights=y.astype(np.float64)).astype(np.int64), np.abs(y).max()
+
+
+def _feedback(fs, kind):
+    """30 epochs of three jobs, w0 of -2^31, 2^31 - 1 and 900 Hz, with the loop at the ends of
+    its arguments"""
+    ne, T = 30, -(-fs // 1000)
+    N = (ne + 8) * T                                     # maxkd: epochs up to a fifth longer
+    d = defaults(fs)
+    gains = {"pull0": (0,) + d[1:], "pullall": (ne + 5,) + d[1:], "nogain": (7, 0, 0, 0, 0),
+             "wrap": (15, 2**30, 2**30, 2**30, d[4]), "maxkd": (3,) + d[1:4] + (kd_max(fs),),
+             "zeros": (3,) + d[1:], "negfull": (3,) + d[1:]}[kind]
+    jobs = [(2, 1, -2**31, ne), (11, T // 3, 2**31 - 1, ne), (30, 5, _w(900, fs), ne)]
+    if kind == "zeros":
+        data = np.zeros(4 * N, np.uint8)
+    elif kind == "negfull":
+        data = np.full(2 * N, -32768, "<i2").view(np.uint8)
+    else:
+        data = random_samples(N, 16, fs % 9973 + len(kind))
+    return _finish(fs, 16, N, gains, jobs, data)
+
+
+def _ends_jobs(fs, N, w):
+    """behind job 0 (40 epochs from sample 5): starts at the last sample, at N and far behind it
+    (count 0), n_epoch 0 and 1, and a job that runs out of samples in its eleventh epoch"""
+    return [(3, 5, w, 40), (7, N - 1, w, 5), (8, N, -w, 5), (9, N + 10**6, w, 5), (12, 7, w, 0),
+            (13, 11, -w, 1), (21, N - 21 * fs // 2000, w, 40)]
+
+
+def _ends(fs, kind):
+    """N from the oracle, so that job 0's last epoch ends exactly at N ("exact": 40 epochs) or
+    one sample behind it (39); SC01 with four jobs of every s0 % 4 and N - 0..3 of every N % 4.
+    The pitch is larger than every n_epoch."""
+    fmt = 1 if kind.startswith("sc01") else 16
+    key = ("ends", fs, fmt)
+    w = _w(700, fs)
+    first = [(3, 5, w, 41)] if fmt == 16 else [(3, 4, w, 41)]
+    if key not in _want:
+        N0 = 42 * -(-fs // 1000) + 16
+        data = random_samples(N0, fmt, fs % 9973 + 50 + fmt)
+        rec, count = track(data, fmt, N0, fs, gains_of(fs, 3), first, 41)
+        assert count[0] == 41
+        _want[key] = (data, int(rec["s"][0, 40]))
+    data, N = _want[key]
+    if fmt == 16:
+        N -= kind == "short"
+        jobs = _ends_jobs(fs, N, w)
+    else:
+        N -= int(kind[-1])
+        jobs = [(3 + 5 * k, 4 + k, w if k % 2 == 0 else -w, 40) for k in range(4)]
+    nb = 4 * N if fmt == 16 else (N + 3) // 4
+    return _finish(fs, fmt, N, gains_of(fs, 3), jobs, data[:nb].copy(), pitch=64)
+
+
+def longest_cfg():
+    """(fs, gains) with cs_nom - span one above the bound of gss_trk_check, and the same one
+    step of Kd / 4 further, which the calls reject"""
+    fs = 2000000000
+    kd = kd_max(fs)
+    assert cs_nominal(fs) - (WSPAN + kd // 4 + 2) == CS_MIN + 1
+    return fs, (0, 0, 0, 0, kd), (0, 0, 0, 0, kd + 1)
+
+
+def _longest():
+    """The longest epoch the limits admit, on SC01: 2 GS/s, w0 = -2^31 and the largest Kd.  Both
+    bits of a sample are the late chip times the carrier's sign (w0 is half a cycle a sample), so
+    the late envelope is full, the early one nearly empty, D_dll close to -2^14 and the second
+    epoch's code step close to its floor."""
+    fs, gains, _ = longest_cfg()
+    cs = cs_nominal(fs) + tdiv(-2**31, 1540)
+    N = -(-M // cs) + (1 << 23)
+    i = np.arange(N, dtype=np.int64)
+    x = chips_of(1)[(((i * cs) - HALF) % M) >> 32] * (1 - 2 * (i & 1))
+    return _finish(fs, 1, N, gains, [(1, 0, -2**31, 2)], pack(x, x, 1))
+
+
+def case(name):
+    if name not in _want:
+        kind, _, rest = name.partition("_")
+        if kind == "rate":
+            fs, fmt = rest.split("_sc")
+            _want[name] = _rate(int(fs), dict(RATE_TABLE)[int(fs)], int(fmt))
+        elif kind == "saturating":
+            _want[name] = _saturating(rest == "inverted")
+        elif kind == "feedback":
+            fs, k = rest.split("_")
+            _want[name] = _feedback(int(fs), k)
+        elif kind == "ends":
+            fs, k = rest.split("_", 1)
+            _want[name] = _ends(int(fs), k)
+        else:
+            assert name == LONGEST
+            _want[name] = _longest()
+    return _want[name]
+
+
 # ---- the physical test's inputs --------------------------------------------------------------
 # The first 12.5 s (125 blocks) of the static scenario at 1 MS/s (asked for 12.6 s: the block
 # count of a duration rounds down, and 12.5 gives 124), rendered by the CPU oracle from
