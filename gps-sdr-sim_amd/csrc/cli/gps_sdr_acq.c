@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "gpssim_amd.h"
+#include "cli_rx.h"
 
 static void usage(void)
 {
@@ -29,12 +30,6 @@ static void usage(void)
         "  --grid=<file>    Write the power grid [PRN][bin][tau] as uint64\n");
 }
 
-static int fail(const char *msg)
-{
-    fprintf(stderr, "ERROR: %s\n", msg);
-    return 1;
-}
-
 static int parse_long(const char *s, long lo, long hi, long *out)
 {
     char *end;
@@ -47,39 +42,12 @@ static int parse_long(const char *s, long lo, long hi, long *out)
     return 0;
 }
 
-static int parse_prns(const char *s, uint32_t *mask)
-{
-    *mask = 0;
-    while (*s) {
-        char *end;
-        long a = strtol(s, &end, 10), b;
-        if (end == s)
-            return -1;
-        b = a;
-        if (*end == '-') {
-            s = end + 1;
-            b = strtol(s, &end, 10);
-            if (end == s)
-                return -1;
-        }
-        if (a < 1 || b > 32 || a > b)
-            return -1;
-        for (long p = a; p <= b; p++)
-            *mask |= 1u << (p - 1);
-        if (*end == ',')
-            end++;
-        else if (*end)
-            return -1;
-        s = end;
-    }
-    return *mask ? 0 : -1;
-}
-
 int main(int argc, char **argv)
 {
-    const char *file = NULL, *grid_file = NULL;
-    double fs = 0, t0 = 0, pfa = 1e-3;
-    long bits = 16, coh = 1, ncoh = 10, fmax = 10000, bin_hz = 0, qshift = -1;
+    const char *grid_file = NULL;
+    rx_opts_t o = RX_OPTS_DEFAULT;
+    double pfa = 1e-3;
+    long coh = 1, ncoh = 10, fmax = 10000, bin_hz = 0, qshift = -1;
     uint32_t mask = 0xFFFFFFFFu;
     int host = 0;
     if (argc < 2) {
@@ -89,48 +57,33 @@ int main(int argc, char **argv)
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         char *end;
-        if ((!strcmp(a, "-f") || !strcmp(a, "-s") || !strcmp(a, "-b") || !strcmp(a, "-t"))) {
-            if (i + 1 >= argc) {
-                usage();
-                return 1;
-            }
-            const char *v = argv[++i];
-            if (a[1] == 'f') {
-                file = v;
-            } else if (a[1] == 's') {
-                fs = strtod(v, &end);
-                if (*end || !(fs >= 1000.0) || fs > 2e9 || fs != floor(fs))
-                    return fail("Invalid sampling frequency.");
-            } else if (a[1] == 'b') {
-                if (parse_long(v, 1, 16, &bits) || (bits != 1 && bits != 8 && bits != 16))
-                    return fail("Invalid I/Q data format.");
-            } else {
-                t0 = strtod(v, &end);
-                if (*end || !(t0 >= 0.0))
-                    return fail("Invalid start time.");
-            }
-        } else if (!strncmp(a, "--coh-ms=", 9)) {
+        const int shared = rx_option(argc, argv, &i, &o, usage);
+        if (shared < 0)
+            return 1;
+        if (shared)
+            continue;
+        if (!strncmp(a, "--coh-ms=", 9)) {
             if (parse_long(a + 9, 1, 1000000, &coh))
-                return fail("Invalid coherent window.");
+                return rx_fail("Invalid coherent window.");
         } else if (!strncmp(a, "--ncoh=", 7)) {
             if (parse_long(a + 7, 1, 1000, &ncoh))
-                return fail("Invalid number of windows (1..1000).");
+                return rx_fail("Invalid number of windows (1..1000).");
         } else if (!strncmp(a, "--fmax=", 7)) {
             if (parse_long(a + 7, 0, 1000000000, &fmax))
-                return fail("Invalid Doppler range.");
+                return rx_fail("Invalid Doppler range.");
         } else if (!strncmp(a, "--bin-hz=", 9)) {
             if (parse_long(a + 9, 1, 1000000000, &bin_hz))
-                return fail("Invalid Doppler bin width.");
+                return rx_fail("Invalid Doppler bin width.");
         } else if (!strncmp(a, "--prn=", 6)) {
-            if (parse_prns(a + 6, &mask))
-                return fail("Invalid PRN list (1..32, e.g. 1,3,7-9).");
+            if (rx_parse_prns(a + 6, &mask))
+                return rx_fail("Invalid PRN list (1..32, e.g. 1,3,7-9).");
         } else if (!strncmp(a, "--pfa=", 6)) {
             pfa = strtod(a + 6, &end);
             if (*end || !(pfa > 0.0) || !(pfa < 1.0))
-                return fail("Invalid false-alarm probability.");
+                return rx_fail("Invalid false-alarm probability.");
         } else if (!strncmp(a, "--qshift=", 9)) {
             if (parse_long(a + 9, 0, 24, &qshift))
-                return fail("Invalid quantiser shift (0..24).");
+                return rx_fail("Invalid quantiser shift (0..24).");
         } else if (!strcmp(a, "--host")) {
             host = 1;
         } else if (!strncmp(a, "--grid=", 7)) {
@@ -140,10 +93,10 @@ int main(int argc, char **argv)
             return 1;
         }
     }
-    if (!file)
-        return fail("Sample file is not specified.");
-    if (fs == 0)
-        return fail("Sampling frequency is not specified.");
+    if (rx_required(&o))
+        return 1;
+    const double fs = o.fs;
+    const long bits = o.bits;
     if (bin_hz == 0)
         bin_hz = coh <= 500 ? 500 / coh : 1;
 
@@ -165,25 +118,19 @@ int main(int argc, char **argv)
     if (gss_last_error()[0])
         fprintf(stderr, "%s\n", gss_last_error());
 
-    /* the first sample: SC01 packs four to a byte, so its start rounds down to one */
-    int64_t first = (int64_t)floor(t0 * fs);
-    if (bits == 1)
-        first -= first % 4;
-    const size_t nbytes = bits == 16 ? (size_t)N * 4 : bits == 8 ? (size_t)N * 2
-                                                                 : (size_t)(N + 3) / 4;
-    const int64_t off = bits == 16 ? first * 4 : bits == 8 ? first * 2 : first / 4;
-    FILE *fp = fopen(file, "rb");
+    const int64_t first = rx_first_sample(&o);
+    FILE *fp = fopen(o.file, "rb");
     if (!fp)
-        return fail("Failed to open the sample file.");
-    void *x = malloc(nbytes);
+        return rx_fail("Failed to open the sample file.");
+    void *x = malloc(rx_bytes(bits, N));
     const size_t nbin = (size_t)(2 * acq.n_half + 1);
     gss_acq_peak_t *peaks = (gss_acq_peak_t *)calloc((size_t)n_prn, sizeof *peaks);
     uint64_t *grid = grid_file ? (uint64_t *)malloc((size_t)n_prn * nbin * T * 8) : NULL;
     if (!x || !peaks || (grid_file && !grid))
-        return fail("Out of memory.");
-    if (fseeko(fp, (off_t)off, SEEK_SET) != 0 || fread(x, 1, nbytes, fp) != nbytes) {
+        return rx_fail("Out of memory.");
+    if (rx_read(fp, bits, first, N, x)) {
         fclose(fp);
-        return fail("The sample file is too short for this search.");
+        return rx_fail("The sample file is too short for this search.");
     }
     fclose(fp);
 
@@ -206,9 +153,7 @@ int main(int argc, char **argv)
     fprintf(stderr, "Search: %lld samples from %lld, %zu bins of %d Hz, shift = %d, "
             "threshold = %.4f\n", (long long)N, (long long)first, nbin, acq.bin_hz, sh, thr);
     for (int p = 0; p < n_prn; p++) {
-        const double ratio = peaks[p].floor_sum
-            ? (double)peaks[p].peak * (double)peaks[p].floor_cnt / (double)peaks[p].floor_sum
-            : 0.0;
+        const double ratio = rx_peak_ratio(&peaks[p]);
         const double cn0 = ratio > 1.0 ? 10.0 * log10((ratio - 1.0) / (acq.coh_ms * 1e-3))
                                        : -INFINITY;
         printf("%2d %d %d %d %.6f %.3f\n", peaks[p].prn, ratio >= thr, peaks[p].tau,
@@ -218,7 +163,7 @@ int main(int argc, char **argv)
         FILE *g = fopen(grid_file, "wb");
         const size_t cells = (size_t)n_prn * nbin * T;
         if (!g || fwrite(grid, 8, cells, g) != cells)
-            return fail("Failed to write the grid file.");
+            return rx_fail("Failed to write the grid file.");
         fclose(g);
     }
     free(x);

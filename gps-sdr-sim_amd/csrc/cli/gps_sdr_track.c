@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "gpssim_amd.h"
+#include "cli_rx.h"
 
 #define LOCK_CN0  28.0           /* tracked C/N0 [dB-Hz] at or above which the line says lock 1  */
 #define MAX_SF    64
@@ -39,50 +40,12 @@ static void usage(void)
         "lock is 1 when the tracked C/N0 is at least 28 dB-Hz.\n");
 }
 
-static int fail(const char *msg)
-{
-    fprintf(stderr, "ERROR: %s\n", msg);
-    return 1;
-}
-
-static int parse_prns(const char *s, uint32_t *mask)
-{
-    *mask = 0;
-    while (*s) {
-        char *end;
-        long a = strtol(s, &end, 10), b;
-        if (end == s)
-            return -1;
-        b = a;
-        if (*end == '-') {
-            s = end + 1;
-            b = strtol(s, &end, 10);
-            if (end == s)
-                return -1;
-        }
-        if (a < 1 || b > 32 || a > b)
-            return -1;
-        for (long p = a; p <= b; p++)
-            *mask |= 1u << (p - 1);
-        if (*end == ',')
-            end++;
-        else if (*end)
-            return -1;
-        s = end;
-    }
-    return *mask ? 0 : -1;
-}
-
-static size_t bytes_of(int bits, int64_t n)
-{
-    return bits == 16 ? (size_t)n * 4 : bits == 8 ? (size_t)n * 2 : (size_t)(n + 3) / 4;
-}
-
 int main(int argc, char **argv)
 {
-    const char *file = NULL, *rec_file = NULL;
-    double fs = 0, t0 = 0, dur = -1, split = 0;
-    long bits = 16, fmax = 5000;
+    const char *rec_file = NULL;
+    rx_opts_t o = RX_OPTS_DEFAULT;
+    double dur = -1, split = 0;
+    long fmax = 5000;
     uint32_t mask = 0xFFFFFFFFu;
     int host = 0;
     if (argc < 2) {
@@ -92,43 +55,30 @@ int main(int argc, char **argv)
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         char *end;
-        if (!strcmp(a, "-f") || !strcmp(a, "-s") || !strcmp(a, "-b") || !strcmp(a, "-t") ||
-            !strcmp(a, "-d")) {
+        const int shared = rx_option(argc, argv, &i, &o, usage);
+        if (shared < 0)
+            return 1;
+        if (shared)
+            continue;
+        if (!strcmp(a, "-d")) {
             if (i + 1 >= argc) {
                 usage();
                 return 1;
             }
-            const char *v = argv[++i];
-            if (a[1] == 'f') {
-                file = v;
-            } else if (a[1] == 's') {
-                fs = strtod(v, &end);
-                if (*end || !(fs >= 1000.0) || fs > 2e9 || fs != floor(fs))
-                    return fail("Invalid sampling frequency.");
-            } else if (a[1] == 'b') {
-                bits = strtol(v, &end, 10);
-                if (*end || (bits != 1 && bits != 8 && bits != 16))
-                    return fail("Invalid I/Q data format.");
-            } else if (a[1] == 't') {
-                t0 = strtod(v, &end);
-                if (*end || !(t0 >= 0.0))
-                    return fail("Invalid start time.");
-            } else {
-                dur = strtod(v, &end);
-                if (*end || !(dur > 0.0))
-                    return fail("Invalid duration.");
-            }
+            dur = strtod(argv[++i], &end);
+            if (*end || !(dur > 0.0))
+                return rx_fail("Invalid duration.");
         } else if (!strncmp(a, "--prn=", 6)) {
-            if (parse_prns(a + 6, &mask))
-                return fail("Invalid PRN list (1..32, e.g. 1,3,7-9).");
+            if (rx_parse_prns(a + 6, &mask))
+                return rx_fail("Invalid PRN list (1..32, e.g. 1,3,7-9).");
         } else if (!strncmp(a, "--fmax=", 7)) {
             fmax = strtol(a + 7, &end, 10);
             if (*end || fmax < 0 || fmax > 1000000)
-                return fail("Invalid Doppler range.");
+                return rx_fail("Invalid Doppler range.");
         } else if (!strncmp(a, "--split=", 8)) {
             split = strtod(a + 8, &end);
             if (*end || !(split > 0.0))
-                return fail("Invalid window length.");
+                return rx_fail("Invalid window length.");
         } else if (!strncmp(a, "--records=", 10)) {
             rec_file = a + 10;
         } else if (!strcmp(a, "--host")) {
@@ -138,10 +88,10 @@ int main(int argc, char **argv)
             return 1;
         }
     }
-    if (!file)
-        return fail("Sample file is not specified.");
-    if (fs == 0)
-        return fail("Sampling frequency is not specified.");
+    if (rx_required(&o))
+        return 1;
+    const double fs = o.fs;
+    const long bits = o.bits;
 
     gss_acq_t acq;
     acq.fs_hz = (int32_t)fs;
@@ -162,14 +112,12 @@ int main(int argc, char **argv)
     }
 
     /* the range: SC01 packs four samples to a byte, so its start and its windows round down */
-    FILE *fp = fopen(file, "rb");
+    FILE *fp = fopen(o.file, "rb");
     if (!fp || fseeko(fp, 0, SEEK_END) != 0)
-        return fail("Failed to open the sample file.");
+        return rx_fail("Failed to open the sample file.");
     const int64_t fbytes = (int64_t)ftello(fp);
     const int64_t in_file = bits == 16 ? fbytes / 4 : bits == 8 ? fbytes / 2 : fbytes * 4;
-    int64_t first = (int64_t)floor(t0 * fs);
-    if (bits == 1)
-        first -= first % 4;
+    const int64_t first = rx_first_sample(&o);
     int64_t N = in_file - first;
     if (dur > 0 && (int64_t)floor(dur * fs) < N)
         N = (int64_t)floor(dur * fs);
@@ -178,17 +126,15 @@ int main(int argc, char **argv)
         win -= win % 4;
     const int32_t n_epoch = win > T ? (int32_t)((win - T) * 1000 / (int64_t)fs) - 1 : 0;
     if (N < 1 || win < n_acq || win > N || n_epoch < 1)
-        return fail("The range or the window is too short to acquire and track.");
+        return rx_fail("The range or the window is too short to acquire and track.");
     const int n_win = (int)(N / win);
     N = (int64_t)n_win * win;
-    void *x = malloc(bytes_of((int)bits, N));
+    void *x = malloc(rx_bytes(bits, N));
     if (!x)
-        return fail("Out of memory.");
-    if (fseeko(fp, (off_t)(bits == 16 ? first * 4 : bits == 8 ? first * 2 : first / 4),
-               SEEK_SET) != 0 ||
-        fread(x, 1, bytes_of((int)bits, N), fp) != bytes_of((int)bits, N)) {
+        return rx_fail("Out of memory.");
+    if (rx_read(fp, bits, first, N, x)) {
         fclose(fp);
-        return fail("Failed to read the sample file.");
+        return rx_fail("Failed to read the sample file.");
     }
     fclose(fp);
 
@@ -200,18 +146,15 @@ int main(int argc, char **argv)
     gss_trk_job_t *jobs = (gss_trk_job_t *)calloc((size_t)n_win * n_prn, sizeof *jobs);
     int *job_win = (int *)calloc((size_t)n_win * n_prn, sizeof *job_win);
     if (!peaks || !jobs || !job_win)
-        return fail("Out of memory.");
+        return rx_fail("Out of memory.");
     int n_job = 0;
     for (int k = 0; k < n_win && rc == 0; k++) {
         const int64_t w0 = (int64_t)k * win;
-        const void *xw = (const char *)x + (bits == 16 ? w0 * 4 : bits == 8 ? w0 * 2 : w0 / 4);
+        const void *xw = (const char *)x + rx_offset(bits, w0);
         rc = host ? gss_acquire_host(&acq, xw, peaks, NULL, NULL, 16)
                   : gss_acquire(dev, &acq, xw, peaks, NULL, NULL);
         for (int p = 0; p < n_prn && rc == 0; p++) {
-            const double ratio = peaks[p].floor_sum
-                ? (double)peaks[p].peak * (double)peaks[p].floor_cnt / (double)peaks[p].floor_sum
-                : 0.0;
-            if (ratio < thr)
+            if (rx_peak_ratio(&peaks[p]) < thr)
                 continue;
             rc = gss_trk_job_from_peak(&acq, &peaks[p], w0, n_epoch, &jobs[n_job]);
             job_win[n_job++] = k;
@@ -223,7 +166,7 @@ int main(int argc, char **argv)
         rec = (gss_trk_rec_t *)malloc((size_t)n_job * n_epoch * sizeof *rec);
         count = (int32_t *)calloc((size_t)n_job, sizeof *count);
         if (!rec || !count)
-            return fail("Out of memory.");
+            return rx_fail("Out of memory.");
         rc = host ? gss_track_host(&cfg, x, N, jobs, n_job, rec, n_epoch, count, 16)
                   : gss_track(dev, &cfg, x, N, jobs, n_job, rec, n_epoch, count);
     }
@@ -238,7 +181,7 @@ int main(int argc, char **argv)
 
     FILE *rf = rec_file ? fopen(rec_file, "wb") : NULL;
     if (rec_file && !rf)
-        return fail("Failed to open the records file.");
+        return rx_fail("Failed to open the records file.");
     for (int j = 0; j < n_job; j++) {
         const gss_trk_rec_t *r = rec + (size_t)j * n_epoch;
         gss_nav_sf_t sf[MAX_SF];
@@ -256,7 +199,7 @@ int main(int argc, char **argv)
             printf("SF %2d window %d sample %lld tow %d id %d\n", jobs[j].prn, job_win[j],
                    (long long)(first + sf[k].sample), sf[k].tow, sf[k].id);
         if (rf && fwrite(r, sizeof *r, (size_t)count[j], rf) != (size_t)count[j])
-            return fail("Failed to write the records file.");
+            return rx_fail("Failed to write the records file.");
     }
     if (rf)
         fclose(rf);

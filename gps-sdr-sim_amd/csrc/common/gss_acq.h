@@ -91,6 +91,13 @@ GSS_ACQ_HD void gss_acq_sample(const void *s, int fmt, int64_t n, int32_t *xi, i
     }
 }
 
+/* the bytes that hold n samples (SC01: whole bytes, four samples each) */
+GSS_ACQ_HD size_t gss_acq_bytes(int fmt, int64_t n)
+{
+    return fmt == GSS_FMT_SC16 ? (size_t)n * 4 : fmt == GSS_FMT_SC08 ? (size_t)n * 2
+                                                                     : (size_t)(n + 3) / 4;
+}
+
 /* the automatic shift from the input's component maxima */
 GSS_ACQ_HD int32_t gss_acq_auto_shift(int32_t max_i, int32_t max_q)
 {

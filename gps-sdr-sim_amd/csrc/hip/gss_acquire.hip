@@ -30,12 +30,10 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <mutex>
 #include "gpssim_amd.h"
+#include "gss_dev.h"
 #include "../common/gss_acq.h"
 
-extern "C" int gss_fail(int code, const char *fmt, ...);
-extern "C" int gss_dev_ordinal(const gss_dev *d);
 extern "C" int gss_acq_check(const gss_acq_t *a, gss_acq_dims_t *d);        /* acquire.c */
 
 namespace {
@@ -364,59 +362,6 @@ __global__ __launch_bounds__(ACQ_THREADS) void gss_acq_peak_kernel(AcqArgs A)
     }
 }
 
-/* the scratch of one device: kept for the process, grown on demand (hipFree waits for the
-   device, so a search still in flight finishes first) */
-struct AcqScratch {
-    int8_t *planes = nullptr, *rep = nullptr;
-    uint64_t *rows = nullptr, *cand = nullptr;
-    size_t planes_cap = 0, rep_cap = 0, rows_cap = 0, cand_cap = 0;
-    int32_t *maxes = nullptr;
-    uint32_t *ca = nullptr;
-    int16_t *lut = nullptr;
-};
-std::mutex scr_mu;
-AcqScratch scr[64];
-
-template <class T> int grow(T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap)
-        return 0;
-    if (p)
-        (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc((void **)&p, need) != hipSuccess) {
-        p = nullptr;
-        return gss_fail(GSS_E_NOMEM, "acquisition scratch: %zu bytes of device memory", need);
-    }
-    cap = need;
-    return 0;
-}
-
-int scratch_tables(AcqScratch &s)
-{
-    if (s.lut)
-        return 0;
-    uint32_t ca[32 * GSS_CA_WORDS];
-    int32_t sn[512], cs[512];
-    int16_t lut[1024];
-    gss_ca_table(ca);
-    gss_lut(sn, cs);
-    for (int i = 0; i < 512; i++) {
-        lut[i] = (int16_t)cs[i];
-        lut[512 + i] = (int16_t)sn[i];
-    }
-    int16_t *dl = nullptr;
-    if (hipMalloc((void **)&s.maxes, 2 * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void **)&s.ca, sizeof ca) != hipSuccess ||
-        hipMalloc((void **)&dl, sizeof lut) != hipSuccess ||
-        hipMemcpy(s.ca, ca, sizeof ca, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dl, lut, sizeof lut, hipMemcpyHostToDevice) != hipSuccess)
-        return gss_fail(GSS_E_HIP, "acquisition tables: %s", hipGetErrorString(hipGetLastError()));
-    s.lut = dl;
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int gss_acquire_device(gss_dev *d, const gss_acq_t *a, const void *d_samples,
@@ -430,10 +375,7 @@ extern "C" int gss_acquire_device(gss_dev *d, const gss_acq_t *a, const void *d_
     if (!d || !d_samples || !d_peaks || (a->fmt == GSS_FMT_SC16 && ((uintptr_t)d_samples & 1)) ||
         ((uintptr_t)d_peaks & 7) || ((uintptr_t)d_grid & 7) || ((uintptr_t)d_qshift & 3))
         return gss_fail(GSS_E_ARG, "invalid acquisition buffers");
-    const int dev = gss_dev_ordinal(d);
-    if (dev < 0 || dev >= 64)
-        return gss_fail(GSS_E_ARG, "device ordinal %d", dev);
-    if (hipSetDevice(dev) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
 
     AcqArgs A;
@@ -447,26 +389,28 @@ extern "C" int gss_acquire_device(gss_dev *d, const gss_acq_t *a, const void *d_
     for (int p = 0; p < dm.n_prn; p++)
         A.prn[p] = (uint8_t)dm.prn[p];
 
-    std::lock_guard<std::mutex> lk(scr_mu);
-    AcqScratch &s = scr[dev];
-    if ((rc = scratch_tables(s)) != 0 ||
-        (rc = grow(s.planes, s.planes_cap, (size_t)dm.n_bin * 2 * A.Npad)) != 0 ||
-        (rc = grow(s.rep, s.rep_cap, (size_t)ACQ_SLOTS * A.M * A.Lpad)) != 0 ||
-        (rc = grow(s.cand, s.cand_cap, (size_t)dm.n_prn * dm.n_bin * 12)) != 0)
+    /* the handle's scratch, grown on demand */
+    auto &s = d->acq;
+    const char *what = "acquisition scratch";
+    if ((rc = s.maxes.reserve(2 * sizeof(int32_t), what)) != 0 ||
+        (rc = s.planes.reserve((size_t)dm.n_bin * 2 * A.Npad, what)) != 0 ||
+        (rc = s.rep.reserve((size_t)ACQ_SLOTS * A.M * A.Lpad, what)) != 0 ||
+        (rc = s.cand.reserve((size_t)dm.n_prn * dm.n_bin * 12, what)) != 0)
         return rc;
     if (!d_grid &&
-        (rc = grow(s.rows, s.rows_cap, (size_t)dm.n_prn * dm.n_bin * dm.T * sizeof(uint64_t))) != 0)
+        (rc = s.rows.reserve((size_t)dm.n_prn * dm.n_bin * dm.T * sizeof(uint64_t), what)) != 0)
         return rc;
-    A.x = d_samples; A.planes = s.planes; A.rep = s.rep; A.rows = d_grid ? d_grid : s.rows;
-    A.cand_v = s.cand;
-    A.cand_t = reinterpret_cast<uint32_t *>(s.cand + (size_t)dm.n_prn * dm.n_bin);
-    A.maxes = s.maxes; A.qshift_out = d_qshift; A.peaks = d_peaks; A.ca = s.ca; A.lut = s.lut;
+    A.x = d_samples; A.planes = s.planes.p; A.rep = s.rep.p; A.rows = d_grid ? d_grid : s.rows.p;
+    A.cand_v = s.cand.p;
+    A.cand_t = reinterpret_cast<uint32_t *>(s.cand.p + (size_t)dm.n_prn * dm.n_bin);
+    A.maxes = s.maxes.p; A.qshift_out = d_qshift; A.peaks = d_peaks;
+    A.ca = d->tab.p->ca; A.lut = d->tab.p->lut;
 
     const char *path = getenv("GSS_ACQ_PATH");                 /* read per call: tests switch it */
     const bool valu = path && strcmp(path, "valu") == 0;
     hipStream_t st = (hipStream_t)stream;
     if (a->qshift < 0) {
-        if (hipMemsetAsync(s.maxes, 0, 2 * sizeof(int32_t), st) != hipSuccess)
+        if (hipMemsetAsync(s.maxes.p, 0, 2 * sizeof(int32_t), st) != hipSuccess)
             return gss_fail(GSS_E_HIP, "acquisition: hipMemsetAsync failed");
         int64_t gm = (dm.N + ACQ_THREADS - 1) / ACQ_THREADS;
         gm = gm > 1024 ? 1024 : gm;
@@ -497,10 +441,9 @@ extern "C" int gss_acquire(gss_dev *d, const gss_acq_t *a, const void *samples,
         return rc;
     if (!d || !samples || !peaks)
         return gss_fail(GSS_E_ARG, "invalid acquisition buffers");
-    if (hipSetDevice(gss_dev_ordinal(d)) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
-    const size_t nb = a->fmt == GSS_FMT_SC16 ? (size_t)dm.N * 4
-                    : a->fmt == GSS_FMT_SC08 ? (size_t)dm.N * 2 : (size_t)(dm.N + 3) / 4;
+    const size_t nb = gss_acq_bytes(a->fmt, dm.N);
     const size_t pb = (size_t)dm.n_prn * sizeof(gss_acq_peak_t);
     const size_t gbytes = (size_t)dm.n_prn * dm.n_bin * dm.T * sizeof(uint64_t);
     void *dx = nullptr, *dp = nullptr, *dg = nullptr, *dq = nullptr;

@@ -17,12 +17,10 @@
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <mutex>
 #include "gpssim_amd.h"
+#include "gss_dev.h"
 #include "../common/gss_impair.h"
 
-extern "C" int gss_fail(int code, const char *fmt, ...);
-extern "C" int gss_dev_ordinal(const gss_dev *d);
 extern "C" int gss_impair_check(const gss_impair_t *p, const void *iq, uint64_t sample0, size_t n,
                                 int fmt, const void *out);                    /* impair.c */
 
@@ -31,12 +29,10 @@ namespace {
 constexpr int IMP_THREADS = 256;
 constexpr int IMP_GRID_MAX = 2048;
 
-/* the table on the device (gss_noise_table, uploaded once per device) */
-__device__ int32_t gss_imp_tbl_dev[GSS_IMP_TBL];
-
 struct ImpArgs {
     const int16_t *iq;
     void *out;
+    const int32_t *tbl;     /* gss_noise_table on the device (the handle's, made at open)        */
     uint64_t sample0;       /* absolute index of iq's first sample                              */
     uint64_t n;             /* samples                                                          */
     uint64_t head;          /* samples before the first whole group (multiple of 4 for SC01)    */
@@ -138,11 +134,11 @@ __global__ __launch_bounds__(IMP_THREADS) void gss_impair_kernel(ImpArgs A)
 {
     constexpr int NS = 4 * ImpFmt<FMT>::U, ITEM = ImpFmt<FMT>::ITEM;
 #ifdef GSS_IMP_TBL_L2                 /* measurement build: the cells from global memory (L2) */
-    const int32_t *T = gss_imp_tbl_dev;
+    const int32_t *T = A.tbl;
 #else
     __shared__ int32_t T[GSS_IMP_TBL];
     for (int i = threadIdx.x; i < GSS_IMP_TBL; i += IMP_THREADS)
-        T[i] = gss_imp_tbl_dev[i];
+        T[i] = A.tbl[i];
     __syncthreads();
 #endif
     const uint64_t t0 = (uint64_t)blockIdx.x * IMP_THREADS + threadIdx.x;
@@ -162,27 +158,6 @@ __global__ __launch_bounds__(IMP_THREADS) void gss_impair_kernel(ImpArgs A)
     }
 }
 
-std::mutex tbl_mu;
-bool tbl_up[64];
-
-int table_upload(int dev)
-{
-    if (dev < 0 || dev >= 64)
-        return gss_fail(GSS_E_ARG, "device ordinal %d", dev);
-    std::lock_guard<std::mutex> lk(tbl_mu);
-    if (tbl_up[dev])
-        return 0;
-    int32_t t[GSS_IMP_TBL];
-    int rc = gss_noise_table(t);
-    if (rc)
-        return rc;
-    const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(gss_imp_tbl_dev), t, sizeof t);
-    if (e != hipSuccess)
-        return gss_fail(GSS_E_HIP, "noise table upload: %s", hipGetErrorString(e));
-    tbl_up[dev] = true;
-    return 0;
-}
-
 template <int FMT> void launch(const ImpArgs &A, unsigned grid, hipStream_t st)
 {
     hipLaunchKernelGGL(gss_impair_kernel<FMT>, dim3(grid), dim3(IMP_THREADS), 0, st, A);
@@ -198,18 +173,15 @@ extern "C" int gss_impair_device(gss_dev *d, const gss_impair_t *p, const int16_
     int rc = gss_impair_check(p, iq, sample0, n, fmt, out);
     if (rc || n == 0)
         return rc;
-    const int dev = gss_dev_ordinal(d);
-    if (hipSetDevice(dev) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
-    if ((rc = table_upload(dev)) != 0)
-        return rc;
     const int U = fmt == GSS_FMT_SC16 ? 1 : fmt == GSS_FMT_SC08 ? 2 : 4;
     const int item = fmt == GSS_FMT_SC01 ? 4 : 1;
     const size_t ns = (size_t)4 * U;
     /* the least head after which the input is 16-byte aligned and the output aligned to its
        store (16, 16, 4 bytes); none (pointers that never line up): every sample by the edges */
     ImpArgs A;
-    A.iq = iq; A.out = out; A.sample0 = sample0; A.n = n;
+    A.iq = iq; A.out = out; A.tbl = d->tab.p->noise; A.sample0 = sample0; A.n = n;
     A.k0 = (uint32_t)p->seed; A.k1 = (uint32_t)(p->seed >> 32);
     A.sigma_q8 = p->sigma_q8; A.shift = p->shift;
     A.head = n;

@@ -11,11 +11,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "gpssim_amd.h"
+#include "gss_dev.h"
 #include "../common/gss_nav.h"
 #include "../common/gss_phase.h"
-
-extern "C" int gss_fail(int code, const char *fmt, ...);
-extern "C" int gss_dev_ordinal(const gss_dev *d);
 
 /* one workgroup of 64 lanes: lane 0 runs the two 10-stage registers (1023 steps), then the wave
    forms each PRN's chips 64 at a time and packs them with a ballot */
@@ -58,7 +56,7 @@ extern "C" int gss_ca_table_device(gss_dev *d, uint32_t *out, void *stream)
 {
     if (!d || !out)
         return gss_fail(GSS_E_ARG, "invalid C/A table arguments");
-    if (hipSetDevice(gss_dev_ordinal(d)) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
     hipLaunchKernelGGL(gss_ca_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, out);
     const hipError_t e = hipGetLastError();
@@ -72,7 +70,7 @@ extern "C" int gss_nav_rows_device(gss_dev *d, const gss_nav_src_t *src, int fir
         return gss_fail(GSS_E_ARG, "invalid nav-row arguments");
     if (n == 0)
         return 0;
-    if (hipSetDevice(gss_dev_ordinal(d)) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
     hipLaunchKernelGGL(gss_nav_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0,
                        (hipStream_t)stream, src, first, n, rows);
@@ -473,7 +471,7 @@ extern "C" int gss_spec_records_device(gss_dev *d, const gss_spec_in_t *in, int 
                         "and records 16-byte aligned, in and d_in apart)");
     if (nrow == 0)
         return 0;
-    if (hipSetDevice(gss_dev_ordinal(d)) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
     hipLaunchKernelGGL(gss_spec_kernel, dim3((unsigned)((nrow + SPEC_ROWS - 1) / SPEC_ROWS)),
                        dim3(64), 0, (hipStream_t)stream, in, d_in, nrow, n_per_blk, d_spec, 1);
@@ -493,7 +491,7 @@ extern "C" int gss_spec_device(gss_dev *d, gss_spec_in_t *in, int nrow, int n_pe
                         "16-byte aligned)");
     if (nrow == 0)
         return 0;
-    if (hipSetDevice(gss_dev_ordinal(d)) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
     hipLaunchKernelGGL(gss_spec_kernel, dim3((unsigned)((nrow + SPEC_ROWS - 1) / SPEC_ROWS)),
                        dim3(64), 0,

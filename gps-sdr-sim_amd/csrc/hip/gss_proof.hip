@@ -15,10 +15,8 @@
 #include <string.h>
 #include <mutex>
 #include "gpssim_amd.h"
+#include "gss_dev.h"
 #include "../common/gss_proof.h"
-
-extern "C" int gss_fail(int code, const char *fmt, ...);
-extern "C" int gss_dev_ordinal(const gss_dev *d);
 
 namespace {
 
@@ -222,7 +220,7 @@ extern "C" int gss_linearize_device_ex(gss_dev *d, const gss_chan_blk_t *blk, co
     if (!d || !blk || !nch || !lin || !fast || nblk < 0 || n_per_blk <= 0 ||
         (n_nav > 0 && !nav) || (n_ca > 0 && !ca_bits) || n_ca < 0)
         return gss_fail(GSS_E_ARG, "invalid linearize_device arguments");
-    if (hipSetDevice(gss_dev_ordinal(d)) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice");
     return run_proof_launch(blk, nch, nblk, n_per_blk, ca_bits, n_ca, nav, n_nav, anch, nullptr,
                             nullptr, lin, fast, 0, 0, (hipStream_t)stream);

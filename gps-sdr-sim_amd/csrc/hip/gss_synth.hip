@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "gpssim_amd.h"
+#include "gss_dev.h"
 #include "../common/gss_phase.h"
 #include "../common/gss_lin.h"
 
@@ -36,8 +37,6 @@
 #define CHUNK_BYTES    128               /* output bytes per lane per staged chunk: a line */
 #define CHUNK_PIECES   (CHUNK_BYTES / 16)
 #define LUT_N          1024              /* index ti + 256*neg <= 767; padded to a power of 2 */
-
-struct lut_arg { int16_t sin512[512]; int16_t cos512[512]; };
 
 /* ======================================================================================== */
 /* Stage A: anchors                                                                         */
@@ -1281,42 +1280,6 @@ void gss_lin_kernel(
 /* ======================================================================================== */
 /* C ABI                                                                                    */
 /* ======================================================================================== */
-struct gss_dev {
-    int ordinal;
-    int seg_r = 1024;                    /* samples per Stage-B lane (env GSS_SEG_R)   */
-    struct anchor_set {                  /* segment-start states [blocks][16][nsegp]     */
-        double *carr = nullptr, *code = nullptr;
-        uint32_t *cnt = nullptr;
-        size_t cap = 0;
-    } set[2];                            /* two sets: Stage A of batch k+1 beside B of k  */
-    static constexpr int RING = 256;
-    hipEvent_t ev_a[RING][2], ev_b[RING][2];   /* start/end of each stage launch          */
-    hipEvent_t ev_l[RING][2];                  /* ... and of each fast-path launch         */
-    int n_a = 0, n_b = 0, n_l = 0;
-    lut_arg lut;
-    uint4 *d_lut16 = nullptr;            /* the fast kernel's LUT: (cos, sin) f16 pairs, the
-                                            second half negated; made once (gss_dev_open)  */
-    void *h_in = nullptr; size_t h_in_cap = 0;
-    void *d_out = nullptr; size_t d_out_cap = 0;
-    double *d_cend = nullptr; size_t d_cend_cap = 0;
-    uint32_t *d_cbw = nullptr; size_t d_cbw_cap = 0;   /* chip-sign bit-streams (gss_cab_kernel) */
-    int32_t *d_status = nullptr;
-    /* the exact path's leftovers of a fast-path call run on their own stream beside the fast
-       kernel (a few latency-bound blocks would otherwise serialise after it) */
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_in = nullptr, ev_fb = nullptr;
-};
-
-extern "C" int gss_fail(int code, const char *fmt, ...);
-
-#define HIP_TRY(x)                                                                           \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess)                                                                \
-            return gss_fail(GSS_E_HIP, "HIP error %s at %s:%d", hipGetErrorString(e_),      \
-                            __FILE__, __LINE__);                                             \
-    } while (0)
-
 #define GSS_STR2(x) #x
 #define GSS_STR(x) GSS_STR2(x)
 /* the device ordinal of an open handle (gss_producers.hip, gss_run.hip) */
@@ -1330,6 +1293,60 @@ extern "C" const char *gss_build_info(void)
 
 
 extern "C" void gss_run_pool_prewarm(int dev);    /* gss_run.hip */
+extern "C" void gss_run_pool_drain(int dev);
+
+/* The tables of a handle as the host makes them, once per process (the C/A codes alone take
+   about half a millisecond): the device's image and the exact path's by-value LUT. */
+struct host_tables {
+    gss_dev_tables dev;
+    lut_arg lut;
+};
+
+static const host_tables &tables_once()
+{
+    static const host_tables made = [] {
+        host_tables h;
+        int32_t s[512], c[512];
+        gss_lut(s, c);
+        for (int i = 0; i < 512; i++) {
+            h.lut.sin512[i] = h.dev.lut[512 + i] = (int16_t)s[i];
+            h.lut.cos512[i] = h.dev.lut[i] = (int16_t)c[i];
+            const uint32_t v = lin_f16_bits(c[i]) | (lin_f16_bits(s[i]) << 16);
+            h.dev.lut16[i] = v;
+            h.dev.lut16[512 + i] = v ^ 0x80008000u;
+        }
+        gss_ca_table(h.dev.ca);
+        gss_noise_table(h.dev.noise);    /* fails for a null argument only */
+        return h;
+    }();
+    return made;
+}
+
+static int dev_init(gss_dev *d)
+{
+    const char *r = getenv("GSS_SEG_R");
+    if (r && atoi(r) >= 256 && atoi(r) % 256 == 0)
+        d->seg_r = atoi(r);
+    for (int i = 0; i < gss_dev::RING; i++)
+        for (int j = 0; j < 2; j++) {
+            HIP_TRY(hipEventCreate(&d->ev_a[i][j]));
+            HIP_TRY(hipEventCreate(&d->ev_b[i][j]));
+            HIP_TRY(hipEventCreate(&d->ev_l[i][j]));
+        }
+    const host_tables &h = tables_once();
+    d->lut = h.lut;
+    int rc = d->tab.reserve(sizeof h.dev, "constant tables");
+    if (rc == 0) rc = d->d_status.reserve(sizeof(int32_t), "render status");
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(d->tab.p, &h.dev, sizeof h.dev, hipMemcpyHostToDevice));
+    int prio_lo = 0, prio_hi = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    HIP_TRY(hipStreamCreateWithPriority(&d->aux, hipStreamNonBlocking, prio_hi));
+    HIP_TRY(hipEventCreateWithFlags(&d->ev_in, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&d->ev_fb, hipEventDisableTiming));
+    gss_run_pool_prewarm(d->ordinal);                /* gss_run's streams, made once here */
+    return 0;
+}
 
 extern "C" int gss_dev_open(gss_dev **out, int ordinal)
 {
@@ -1342,65 +1359,47 @@ extern "C" int gss_dev_open(gss_dev **out, int ordinal)
     HIP_TRY(hipSetDevice(ordinal));
     gss_dev *d = new gss_dev();
     d->ordinal = ordinal;
-    const char *r = getenv("GSS_SEG_R");
-    if (r && atoi(r) >= 256 && atoi(r) % 256 == 0)
-        d->seg_r = atoi(r);
-    for (int i = 0; i < gss_dev::RING; i++)
-        for (int j = 0; j < 2; j++) {
-            HIP_TRY(hipEventCreate(&d->ev_a[i][j]));
-            HIP_TRY(hipEventCreate(&d->ev_b[i][j]));
-            HIP_TRY(hipEventCreate(&d->ev_l[i][j]));
-        }
-    int32_t s[512], c[512];
-    gss_lut(s, c);
-    for (int i = 0; i < 512; i++) {
-        d->lut.sin512[i] = (int16_t)s[i];
-        d->lut.cos512[i] = (int16_t)c[i];
+    const int rc = dev_init(d);
+    if (rc) {                                        /* what was made so far goes again */
+        gss_dev_close(d);
+        return rc;
     }
-    {
-        uint32_t packed[1024];
-        for (int i = 0; i < 512; i++) {
-            const uint32_t v = lin_f16_bits(c[i]) | (lin_f16_bits(s[i]) << 16);
-            packed[i] = v;
-            packed[512 + i] = v ^ 0x80008000u;
-        }
-        HIP_TRY(hipMalloc(&d->d_lut16, sizeof(packed)));
-        HIP_TRY(hipMemcpy(d->d_lut16, packed, sizeof(packed), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMalloc(&d->d_status, sizeof(int32_t)));
-    int prio_lo = 0, prio_hi = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    HIP_TRY(hipStreamCreateWithPriority(&d->aux, hipStreamNonBlocking, prio_hi));
-    HIP_TRY(hipEventCreateWithFlags(&d->ev_in, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&d->ev_fb, hipEventDisableTiming));
-    gss_run_pool_prewarm(ordinal);                   /* gss_run's streams, made once here */
     *out = d;
     return 0;
 }
 
-extern "C" void gss_run_pool_drain(int dev);      /* gss_run.hip */
-
+/* every buffer gss_dev declares is released here */
 extern "C" int gss_dev_close(gss_dev *d)
 {
     if (!d) return 0;
     (void)hipSetDevice(d->ordinal);
     gss_run_pool_drain(d->ordinal);                  /* gss_run's pooled slot buffers */
     for (auto &a : d->set) {
-        (void)hipFree(a.carr);
-        (void)hipFree(a.code);
-        (void)hipFree(a.cnt);
+        a.carr.release();
+        a.code.release();
+        a.cnt.release();
     }
     if (d->aux) (void)hipStreamDestroy(d->aux);
     if (d->ev_in) (void)hipEventDestroy(d->ev_in);
     if (d->ev_fb) (void)hipEventDestroy(d->ev_fb);
-    void *bufs[] = {d->h_in, d->d_out, d->d_cend, d->d_cbw, d->d_lut16, d->d_status};
-    for (void *p : bufs)
-        (void)hipFree(p);
+    d->tab.release();
+    d->d_in.release();
+    d->d_out.release();
+    d->d_cend.release();
+    d->d_cbw.release();
+    d->d_status.release();
+    d->acq.planes.release();
+    d->acq.rep.release();
+    d->acq.rows.release();
+    d->acq.cand.release();
+    d->acq.maxes.release();
+    d->trk.state.release();
+    d->trk.jobs.release();
     for (int i = 0; i < gss_dev::RING; i++)
-        for (int j = 0; j < 2; j++) {
-            (void)hipEventDestroy(d->ev_a[i][j]);
-            (void)hipEventDestroy(d->ev_b[i][j]);
-            (void)hipEventDestroy(d->ev_l[i][j]);
+        for (int j = 0; j < 2; j++) {                /* null after an open that failed early */
+            if (d->ev_a[i][j]) (void)hipEventDestroy(d->ev_a[i][j]);
+            if (d->ev_b[i][j]) (void)hipEventDestroy(d->ev_b[i][j]);
+            if (d->ev_l[i][j]) (void)hipEventDestroy(d->ev_l[i][j]);
         }
     delete d;
     return 0;
@@ -1410,23 +1409,20 @@ static int nseg_of(int n, int r) { return (n + r - 1) / r; }
 /* anchor row stride: the segment starts and one dummy slot (gss_code_seg_states_bf) */
 static int nsegp_of(int n, int r) { return (nseg_of(n, r) + 1 + 31) & ~31; }
 
+/* a set holds its three arrays at one size or none of them */
 static int reserve_set(gss_dev *d, int set, int max_blocks, int n_per_blk, int R)
 {
     gss_dev::anchor_set &a = d->set[set];
-    size_t need = (size_t)max_blocks * GSS_MAXCH * (size_t)nsegp_of(n_per_blk, R);
-    if (need <= a.cap)
-        return 0;
-    (void)hipFree(a.carr);
-    (void)hipFree(a.code);
-    (void)hipFree(a.cnt);
-    a.carr = a.code = nullptr;
-    a.cnt = nullptr;
-    a.cap = 0;
-    HIP_TRY(hipMalloc(&a.carr, need * sizeof(double)));
-    HIP_TRY(hipMalloc(&a.code, need * sizeof(double)));
-    HIP_TRY(hipMalloc(&a.cnt, need * sizeof(uint32_t)));
-    a.cap = need;
-    return 0;
+    const size_t need = (size_t)max_blocks * GSS_MAXCH * (size_t)nsegp_of(n_per_blk, R);
+    int rc = a.carr.reserve(need * sizeof(double), "anchor set");
+    if (rc == 0) rc = a.code.reserve(need * sizeof(double), "anchor set");
+    if (rc == 0) rc = a.cnt.reserve(need * sizeof(uint32_t), "anchor set");
+    if (rc) {
+        a.carr.release();
+        a.code.release();
+        a.cnt.release();
+    }
+    return rc;
 }
 
 extern "C" int gss_dev_reserve(gss_dev *d, int max_blocks, int n_per_blk)
@@ -1491,7 +1487,7 @@ static int anchor_launch(gss_dev *d, int set, const gss_chan_blk_t *blk, const i
     d->n_a++;
     HIP_TRY(hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(gss_anchor_kernel, dim3(a_blocks), dim3(ANCHOR_THREADS), 0, st, blk, nch,
-                       carr_ck, nblk, nchp, n_per_blk, nseg, nsegp, R, a.carr, a.code, a.cnt,
+                       carr_ck, nblk, nchp, n_per_blk, nseg, nsegp, R, a.carr.p, a.code.p, a.cnt.p,
                        carr_end, blist);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[1], st));
@@ -1520,7 +1516,7 @@ static int render_launch(gss_dev *d, int set, const gss_chan_blk_t *blk, const i
         return gss_fail(GSS_E_ARG, "invalid format %d for %d samples/block", fmt, n_per_blk);
     const int nseg = nseg_of(n_per_blk, R), nsegp = nsegp_of(n_per_blk, R);
     const gss_dev::anchor_set &a = d->set[set];
-    if ((size_t)nblk * GSS_MAXCH * (size_t)nsegp > a.cap)
+    if ((size_t)nblk * GSS_MAXCH * (size_t)nsegp * sizeof(uint32_t) > a.cnt.cap)
         return gss_fail(GSS_E_STATE, "anchor set %d holds no Stage A output of this size", set);
     const int nchp = nch_max < 1 ? 1 : nch_max;
     if (nchp > GSS_MAXCH)
@@ -1535,7 +1531,7 @@ static int render_launch(gss_dev *d, int set, const gss_chan_blk_t *blk, const i
     const int wg_per_blk = (nseg + SYNTH_THREADS - 1) / SYNTH_THREADS;
     HIP_TRY(hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(fn, dim3(nblk * wg_per_blk), dim3(SYNTH_THREADS), 0, st, blk, nch, ca_bits,
-                       nav, a.carr, a.code, a.cnt, d->lut, n_per_blk, nseg, nsegp, R, wg_per_blk,
+                       nav, a.carr.p, a.code.p, a.cnt.p, d->lut, n_per_blk, nseg, nsegp, R, wg_per_blk,
                        (uint8_t *)out, bb, status, blist);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[1], st));
@@ -1594,19 +1590,14 @@ extern "C" int gss_synth_lin_device(gss_dev *d, const gss_chan_blk_t *blk, const
        advance): a few µs */
     const size_t ncbw = (size_t)n_ca * CAB_W, ntw = (size_t)n_ca * GSS_LIN_TWE * LIN_CH;
     const size_t tw_off = (ncbw + 63) & ~(size_t)63;
-    if ((tw_off + ntw) * sizeof(uint32_t) > d->d_cbw_cap) {
-        (void)hipFree(d->d_cbw);
-        d->d_cbw = nullptr;
-        d->d_cbw_cap = 0;
-        HIP_TRY(hipMalloc(&d->d_cbw, (tw_off + ntw) * sizeof(uint32_t)));
-        d->d_cbw_cap = (tw_off + ntw) * sizeof(uint32_t);
-    }
+    int rc = d->d_cbw.reserve((tw_off + ntw) * sizeof(uint32_t), "chip-sign streams");
+    if (rc) return rc;
     hipLaunchKernelGGL(gss_cab_kernel, dim3((unsigned)((ncbw + 255) / 256)), dim3(256), 0, st,
-                       ca_bits, n_ca, d->d_cbw);
+                       ca_bits, n_ca, d->d_cbw.p);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(gss_tw16_kernel, dim3((unsigned)((ntw + 255) / 256)), dim3(256), 0, st,
-                       (const uint32_t *)d->d_cbw, n_ca, gss_lin_wstep16(n_per_blk),
-                       d->d_cbw + tw_off);
+                       (const uint32_t *)d->d_cbw.p, n_ca, gss_lin_wstep16(n_per_blk),
+                       d->d_cbw.p + tw_off);
     HIP_TRY(hipGetLastError());
     const int segs = (n_per_blk + 64 * LIN_STEPS - 1) / (64 * LIN_STEPS);
     const int wg_per_blk = (segs + LIN_WAVES - 1) / LIN_WAVES;
@@ -1615,7 +1606,7 @@ extern "C" int gss_synth_lin_device(gss_dev *d, const gss_chan_blk_t *blk, const
         HIP_TRY(hipStreamWaitEvent(d->aux, d->ev_in, 0));
         /* short Stage-B segments (256 samples): few blocks, so latency matters, not work */
         const int R = 256;
-        int rc = anchor_launch(d, 0, blk, nch, nch_max, carr_ck, n_fb, n_per_blk, nullptr,
+        rc = anchor_launch(d, 0, blk, nch, nch_max, carr_ck, n_fb, n_per_blk, nullptr,
                                fb_list, R, d->aux);
         if (rc) return rc;
         rc = render_launch(d, 0, blk, nch, nch_max, ca_bits, nav, n_fb, n_per_blk, fmt, out,
@@ -1627,7 +1618,7 @@ extern "C" int gss_synth_lin_device(gss_dev *d, const gss_chan_blk_t *blk, const
     d->n_l++;
     HIP_TRY(hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(fn, dim3((unsigned)nblk * wg_per_blk), dim3(LIN_THREADS), 0, st, lin,
-                       blk, nch, fast, d->d_cbw, d->d_cbw + tw_off, (const uint4 *)d->d_lut16,
+                       blk, nch, fast, d->d_cbw.p, d->d_cbw.p + tw_off, (const uint4 *)d->tab.p->lut16,
                        n_per_blk, wg_per_blk, (uint8_t *)out, bb);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[1], st));
@@ -1701,17 +1692,6 @@ extern "C" int gss_dev_timing_lin(gss_dev *d, int *n, float *lin_ms)
     return 0;
 }
 
-template <class T> static int grow(T **p, size_t *cap, size_t need)
-{
-    if (need <= *cap) return 0;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc((void **)p, need));
-    *cap = need;
-    return 0;
-}
-
 extern "C" int gss_synth_host(gss_dev *d, const gss_chan_blk_t *blk, const int32_t *nch,
                               const double *carr_ck, const uint32_t *ca_bits, int n_ca, const uint32_t *nav, int n_nav,
                               int nblk, int n_per_blk, int fmt, void *out, double *carr_end)
@@ -1761,8 +1741,20 @@ extern "C" int gss_synth_host(gss_dev *d, const gss_chan_blk_t *blk, const int32
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     size_t tot = al(sz_blk) + al(sz_nch) + al(sz_ca) + al(sz_nav) + al(sz_ck) + al(sz_lin) +
                  al(sz_fast);
-    int rc = grow((uint8_t **)&d->h_in, &d->h_in_cap, tot);
+    int rc = d->d_in.reserve(tot, "render inputs");
     if (rc) return rc;
+    uint8_t *at = d->d_in.p;
+    auto take = [&at, al](size_t sz) { uint8_t *p = at; at += al(sz); return p; };
+    gss_chan_blk_t *d_blk = (gss_chan_blk_t *)take(sz_blk);
+    int32_t *d_nch = (int32_t *)take(sz_nch);
+    uint32_t *d_ca = (uint32_t *)take(sz_ca);
+    uint32_t *d_nav = (uint32_t *)take(sz_nav);
+    double *d_ck = (double *)take(sz_ck);
+    gss_lin_t *d_lin = (gss_lin_t *)take(sz_lin);
+    int32_t *d_fast = (int32_t *)take(sz_fast);
+    if (!carr_ck)
+        d_ck = nullptr;
+    int n_fb = 0;
     if (use_lin) {
         gss_lin_t *h_lin = (gss_lin_t *)malloc(sz_lin);
         int32_t *h_fast = (int32_t *)malloc(sz_fast);
@@ -1772,14 +1764,9 @@ extern "C" int gss_synth_host(gss_dev *d, const gss_chan_blk_t *blk, const int32
             return gss_fail(GSS_E_NOMEM, "out of memory");
         }
         rc = gss_linearize(blk, nch, nblk, n_per_blk, ca_bits, n_ca, nav, n_nav, h_lin, h_fast, 8);
-        int n_fb = 0;
         for (int b = 0; b < nblk; b++)
             if (!h_fast[b])
                 h_fast[nblk + n_fb++] = b;
-        uint8_t *lb = (uint8_t *)d->h_in + al(sz_blk) + al(sz_nch) + al(sz_ca) + al(sz_nav) +
-                      al(sz_ck);
-        gss_lin_t *d_lin = (gss_lin_t *)lb;
-        int32_t *d_fast = (int32_t *)(lb + al(sz_lin));
         if (rc == 0 && hipMemcpy(d_lin, h_lin, sz_lin, hipMemcpyHostToDevice) != hipSuccess)
             rc = gss_fail(GSS_E_HIP, "upload of the fast-path lines failed");
         if (rc == 0 && hipMemcpy(d_fast, h_fast, sz_fast, hipMemcpyHostToDevice) != hipSuccess)
@@ -1787,44 +1774,7 @@ extern "C" int gss_synth_host(gss_dev *d, const gss_chan_blk_t *blk, const int32
         free(h_lin);
         free(h_fast);
         if (rc) return rc;
-        uint8_t *base = (uint8_t *)d->h_in;
-        gss_chan_blk_t *d_blk = (gss_chan_blk_t *)base;
-        int32_t *d_nch = (int32_t *)(base + al(sz_blk));
-        uint32_t *d_ca = (uint32_t *)(base + al(sz_blk) + al(sz_nch));
-        uint32_t *d_nav = (uint32_t *)(base + al(sz_blk) + al(sz_nch) + al(sz_ca));
-        double *d_ck = carr_ck ? (double *)(base + al(sz_blk) + al(sz_nch) + al(sz_ca) +
-                                            al(sz_nav)) : nullptr;
-        if (carr_ck)
-            HIP_TRY(hipMemcpy(d_ck, carr_ck, sz_ck, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_blk, blk, sz_blk, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_nch, nch, sz_nch, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_ca, ca_bits, sz_ca, hipMemcpyHostToDevice));
-        if (n_nav > 0)
-            HIP_TRY(hipMemcpy(d_nav, nav, sz_nav, hipMemcpyHostToDevice));
-        else
-            HIP_TRY(hipMemset(d_nav, 0, sz_nav));
-        rc = grow((uint8_t **)&d->d_out, &d->d_out_cap, bb * (size_t)nblk);
-        if (rc) return rc;
-        HIP_TRY(hipMemset(d->d_status, 0, sizeof(int32_t)));
-        rc = gss_synth_lin_device(d, d_blk, d_nch, maxc, d_lin, d_fast, d_fast + nblk, n_fb, d_ck,
-                                  d_ca, n_ca, d_nav, n_nav, nblk, n_per_blk, fmt, d->d_out,
-                                  d->d_status, nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(out, d->d_out, bb * (size_t)nblk, hipMemcpyDeviceToHost));
-        int32_t stv = 0;
-        HIP_TRY(hipMemcpy(&stv, d->d_status, sizeof stv, hipMemcpyDeviceToHost));
-        if (stv)
-            return gss_fail(GSS_E_RANGE, "nav word index ran past dwrd[59]");
-        return 0;
     }
-    uint8_t *base = (uint8_t *)d->h_in;
-    gss_chan_blk_t *d_blk = (gss_chan_blk_t *)base;
-    int32_t *d_nch = (int32_t *)(base + al(sz_blk));
-    uint32_t *d_ca = (uint32_t *)(base + al(sz_blk) + al(sz_nch));
-    uint32_t *d_nav = (uint32_t *)(base + al(sz_blk) + al(sz_nch) + al(sz_ca));
-    double *d_ck = carr_ck ? (double *)(base + al(sz_blk) + al(sz_nch) + al(sz_ca) + al(sz_nav))
-                           : nullptr;
     if (carr_ck)
         HIP_TRY(hipMemcpy(d_ck, carr_ck, sz_ck, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_blk, blk, sz_blk, hipMemcpyHostToDevice));
@@ -1834,26 +1784,27 @@ extern "C" int gss_synth_host(gss_dev *d, const gss_chan_blk_t *blk, const int32
         HIP_TRY(hipMemcpy(d_nav, nav, sz_nav, hipMemcpyHostToDevice));
     else
         HIP_TRY(hipMemset(d_nav, 0, sz_nav));
-    rc = grow((uint8_t **)&d->d_out, &d->d_out_cap, bb * (size_t)nblk);
+    const size_t sz_cend = sizeof(double) * GSS_MAXCH * (size_t)nblk;
+    rc = d->d_out.reserve(bb * (size_t)nblk, "render output");
+    if (rc == 0 && carr_end)
+        rc = d->d_cend.reserve(sz_cend, "carrier end phases");
     if (rc) return rc;
-    double *d_cend = nullptr;
-    if (carr_end) {
-        rc = grow(&d->d_cend, &d->d_cend_cap, sizeof(double) * GSS_MAXCH * (size_t)nblk);
-        if (rc) return rc;
-        d_cend = d->d_cend;
-    }
-    HIP_TRY(hipMemset(d->d_status, 0, sizeof(int32_t)));
-    rc = gss_synth_device(d, d_blk, d_nch, maxc, d_ck, d_ca, n_ca, d_nav, n_nav, nblk, n_per_blk,
-                          fmt,
-                          d->d_out, d_cend, d->d_status, nullptr);
+    HIP_TRY(hipMemset(d->d_status.p, 0, sizeof(int32_t)));
+    if (use_lin)
+        rc = gss_synth_lin_device(d, d_blk, d_nch, maxc, d_lin, d_fast, d_fast + nblk, n_fb, d_ck,
+                                  d_ca, n_ca, d_nav, n_nav, nblk, n_per_blk, fmt, d->d_out.p,
+                                  d->d_status.p, nullptr);
+    else
+        rc = gss_synth_device(d, d_blk, d_nch, maxc, d_ck, d_ca, n_ca, d_nav, n_nav, nblk,
+                              n_per_blk, fmt, d->d_out.p, carr_end ? d->d_cend.p : nullptr,
+                              d->d_status.p, nullptr);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, d->d_out, bb * (size_t)nblk, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d->d_out.p, bb * (size_t)nblk, hipMemcpyDeviceToHost));
     if (carr_end)
-        HIP_TRY(hipMemcpy(carr_end, d_cend, sizeof(double) * GSS_MAXCH * (size_t)nblk,
-                          hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(carr_end, d->d_cend.p, sz_cend, hipMemcpyDeviceToHost));
     int32_t stv = 0;
-    HIP_TRY(hipMemcpy(&stv, d->d_status, sizeof stv, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&stv, d->d_status.p, sizeof stv, hipMemcpyDeviceToHost));
     if (stv)
         return gss_fail(GSS_E_RANGE, "nav word index ran past dwrd[59]");
     return 0;

@@ -29,12 +29,10 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <mutex>
 #include "gpssim_amd.h"
+#include "gss_dev.h"
 #include "../common/gss_trk.h"
 
-extern "C" int gss_fail(int code, const char *fmt, ...);
-extern "C" int gss_dev_ordinal(const gss_dev *d);
 extern "C" int gss_trk_check_args(const gss_trk_cfg_t *cfg, int64_t N, const gss_trk_job_t *jobs,
                                   int n_job, int64_t pitch);                /* track.c */
 
@@ -276,57 +274,6 @@ __global__ __launch_bounds__(NT) void gss_track_kernel(TrkArgs A)
     }
 }
 
-/* the scratch of one device: kept for the process, grown on demand (hipFree waits for the
-   device, so a call still in flight finishes first) */
-struct TrkScratch {
-    gss_trk_state_t *state = nullptr;
-    gss_trk_job_t *jobs = nullptr;
-    size_t state_cap = 0, jobs_cap = 0;
-    uint32_t *ca = nullptr;
-    int16_t *lut = nullptr;
-};
-std::mutex scr_mu;
-TrkScratch scr[64];
-
-template <class T> int grow(T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap)
-        return 0;
-    if (p)
-        (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc((void **)&p, need) != hipSuccess) {
-        p = nullptr;
-        return gss_fail(GSS_E_NOMEM, "tracking scratch: %zu bytes of device memory", need);
-    }
-    cap = need;
-    return 0;
-}
-
-int scratch_tables(TrkScratch &s)
-{
-    if (s.lut)
-        return 0;
-    uint32_t ca[32 * GSS_CA_WORDS];
-    int32_t sn[512], cs[512];
-    int16_t lut[1024];
-    gss_ca_table(ca);
-    gss_lut(sn, cs);
-    for (int i = 0; i < 512; i++) {
-        lut[i] = (int16_t)cs[i];
-        lut[512 + i] = (int16_t)sn[i];
-    }
-    int16_t *dl = nullptr;
-    if (hipMalloc((void **)&s.ca, sizeof ca) != hipSuccess ||
-        hipMalloc((void **)&dl, sizeof lut) != hipSuccess ||
-        hipMemcpy(s.ca, ca, sizeof ca, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dl, lut, sizeof lut, hipMemcpyHostToDevice) != hipSuccess)
-        return gss_fail(GSS_E_HIP, "tracking tables: %s", hipGetErrorString(hipGetLastError()));
-    s.lut = dl;
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int gss_track_device(gss_dev *d, const gss_trk_cfg_t *cfg, const void *d_samples,
@@ -341,10 +288,7 @@ extern "C" int gss_track_device(gss_dev *d, const gss_trk_cfg_t *cfg, const void
         (cfg->fmt == GSS_FMT_SC16 && ((uintptr_t)d_samples & 1)) || ((uintptr_t)d_rec & 7) ||
         ((uintptr_t)d_count & 3))
         return gss_fail(GSS_E_ARG, "invalid tracking buffers");
-    const int dev = gss_dev_ordinal(d);
-    if (dev < 0 || dev >= 64)
-        return gss_fail(GSS_E_ARG, "device ordinal %d", dev);
-    if (hipSetDevice(dev) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
 
     int chunk = TRK_CHUNK;
@@ -366,22 +310,20 @@ extern "C" int gss_track_device(gss_dev *d, const gss_trk_cfg_t *cfg, const void
     for (int j = 0; j < n_job && N > 0; j++)                    /* no samples: no launch          */
         most = jobs[j].n_epoch > most ? jobs[j].n_epoch : most;
 
-    std::lock_guard<std::mutex> lk(scr_mu);
-    TrkScratch &s = scr[dev];
+    auto &s = d->trk;                                           /* the handle's scratch          */
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = scratch_tables(s)) == 0 &&
-        (rc = grow(s.state, s.state_cap, (size_t)n_job * sizeof(gss_trk_state_t))) == 0 &&
-        (rc = grow(s.jobs, s.jobs_cap, (size_t)n_job * sizeof(gss_trk_job_t))) == 0) {
-        /* the jobs go up synchronously, like the tables: the caller's array is free on return */
-        if (hipMemcpy(s.jobs, jobs, (size_t)n_job * sizeof *jobs, hipMemcpyHostToDevice) !=
+    if ((rc = s.state.reserve((size_t)n_job * sizeof(gss_trk_state_t), "tracking scratch")) == 0 &&
+        (rc = s.jobs.reserve((size_t)n_job * sizeof(gss_trk_job_t), "tracking scratch")) == 0) {
+        /* the jobs go up synchronously: the caller's array is free on return */
+        if (hipMemcpy(s.jobs.p, jobs, (size_t)n_job * sizeof *jobs, hipMemcpyHostToDevice) !=
                 hipSuccess ||
             hipMemsetAsync(d_count, 0, (size_t)n_job * sizeof(int32_t), st) != hipSuccess)
             rc = gss_fail(GSS_E_HIP, "tracking: %s", hipGetErrorString(hipGetLastError()));
     }
     if (rc)
         return rc;
-    A.x = d_samples; A.jobs = s.jobs; A.state = s.state; A.rec = d_rec; A.count = d_count;
-    A.ca = s.ca; A.lut = s.lut;
+    A.x = d_samples; A.jobs = s.jobs.p; A.state = s.state.p; A.rec = d_rec; A.count = d_count;
+    A.ca = d->tab.p->ca; A.lut = d->tab.p->lut;
     for (int32_t done = 0; done < most; done += chunk) {
         A.first = done == 0;
         const dim3 grid((unsigned)n_job);
@@ -411,10 +353,9 @@ extern "C" int gss_track(gss_dev *d, const gss_trk_cfg_t *cfg, const void *sampl
         return rc;
     if (!d || !samples || !rec || !count)
         return gss_fail(GSS_E_ARG, "invalid tracking buffers");
-    if (hipSetDevice(gss_dev_ordinal(d)) != hipSuccess)
+    if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
-    const size_t nb = cfg->fmt == GSS_FMT_SC16 ? (size_t)N * 4
-                    : cfg->fmt == GSS_FMT_SC08 ? (size_t)N * 2 : (size_t)(N + 3) / 4;
+    const size_t nb = gss_acq_bytes(cfg->fmt, N);
     const size_t rb = (size_t)n_job * (size_t)pitch * sizeof(gss_trk_rec_t);
     const size_t cb = (size_t)n_job * sizeof(int32_t);
     void *dx = nullptr, *dr = nullptr, *dc = nullptr;

@@ -229,8 +229,8 @@ int gss_noise_table(int32_t *out);
    out == iq is allowed for SC16 only.                                                         */
 int gss_impair_host(const gss_impair_t *p, const int16_t *iq, uint64_t sample0, size_t n,
                     int fmt, void *out);
-/* The same on the device: device pointers, asynchronous on stream (the first call on a device
-   uploads the table synchronously).                                                           */
+/* The same on the device: device pointers, asynchronous on stream.  The table is the handle's:
+   gss_dev_open uploads it and gss_dev_close frees it.                                         */
 int gss_impair_device(gss_dev *d, const gss_impair_t *p, const int16_t *iq, uint64_t sample0,
                       size_t n, int fmt, void *out, void *stream);
 
@@ -284,9 +284,9 @@ int gss_acquire_host(const gss_acq_t *a, const void *samples, gss_acq_peak_t *pe
                      uint64_t *grid, int *qshift_out, int threads);
 /* The same on the device: device pointers (d_grid, d_qshift may be NULL), asynchronous on stream,
    samples 2-byte aligned (SC08 / SC01: 1-byte).  Scratch (the wiped planes, the replicas and,
-   without d_grid, the power rows) is kept per device and grows on first use, synchronously; one
-   search per device may be in flight.  GSS_ACQ_PATH=valu takes the plain integer correlator
-   instead of the matrix cores (same outputs).                                                 */
+   without d_grid, the power rows) is kept per handle, grows on first use, synchronously, and is
+   freed by gss_dev_close; one search per handle may be in flight.  GSS_ACQ_PATH=valu takes the
+   plain integer correlator instead of the matrix cores (same outputs).                        */
 int gss_acquire_device(gss_dev *d, const gss_acq_t *a, const void *d_samples,
                        gss_acq_peak_t *d_peaks, uint64_t *d_grid, int32_t *d_qshift,
                        void *stream);
@@ -376,7 +376,8 @@ int gss_track_host(const gss_trk_cfg_t *cfg, const void *samples, int64_t N,
 /* The same on the device: d_samples, d_rec (8-byte aligned) and d_count are device pointers,
    jobs is a host array (read before the call returns); asynchronous on stream.  A launch
    advances every job by at most 4096 epochs and leaves its state in device scratch (kept per
-   device, grown on first use, synchronously; one call per device may be in flight).
+   handle, grown on first use, synchronously, freed by gss_dev_close; one call per handle may be
+   in flight).
    GSS_TRK_PATH=plain takes the plain form of the kernel (same records).                        */
 int gss_track_device(gss_dev *d, const gss_trk_cfg_t *cfg, const void *d_samples, int64_t N,
                      const gss_trk_job_t *jobs, int n_job, gss_trk_rec_t *d_rec, int64_t pitch,

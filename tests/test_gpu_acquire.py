@@ -14,6 +14,7 @@ from acq_oracle import SHAPES, random_samples
 pytestmark = pytest.mark.gpu
 
 BIG = (1000000, 1, 8, 10, 500, tuple(range(1, 33)))       # the physical test's search
+LARGE = (2600000, 1, 2, 2, 500, (3, 30))                  # larger than every shape of SHAPES
 GUARD = 64
 
 
@@ -107,14 +108,49 @@ def test_scratch_regrows(dev, monkeypatch, path):
     if path == "valu":
         monkeypatch.setenv("GSS_ACQ_PATH", "valu")
     small = SHAPES[0]
-    large = (2600000, 1, 2 + (path == "valu"), 2, 500, (3, 30))
+    large = LARGE[:2] + (2 + (path == "valu"),) + LARGE[3:]
     for tag, s in (("small", small), ("large", large)):
         data = random_samples(s[0], s[1], s[2], 16, seed=7)
-        wp, wg, wsh = O.acquire(data, s[0], 16, s[1], s[2], s[3], s[4], s[5], -1)
+        wp, wg, wsh = want(("regrow", s), s, 16, data, -1)
         peaks, none, sh = on_device(dev, acq_of(s), data, want_grid=False)
         assert sh == wsh and np.array_equal(peaks, wp), tag
         peaks, grid, sh = on_device(dev, acq_of(s), data)
         assert np.array_equal(grid, wg) and np.array_equal(peaks, wp), tag
+
+
+def test_each_handle_owns_its_scratch(monkeypatch):
+    """Searches alternate between handles of one device, small and large, and go on after a
+    handle is closed and on a handle opened afterwards: a capacity or a pointer shared between
+    handles, or one that survived a close, would show as a wrong grid or a fault."""
+    monkeypatch.delenv("GSS_ACQ_PATH", raising=False)
+
+    def run(d, s, want_grid):
+        data = random_samples(s[0], s[1], s[2], 16, seed=7)
+        wp, wg, wsh = want(("regrow", s), s, 16, data, -1)
+        peaks, grid, sh = on_device(d, acq_of(s), data, want_grid=want_grid)
+        assert sh == wsh and np.array_equal(peaks, wp)
+        assert not want_grid or np.array_equal(grid, wg)
+
+    open_handles = []
+
+    def opened():
+        open_handles.append(G.Device(0))
+        return open_handles[-1]
+
+    try:
+        a = opened()
+        run(a, SHAPES[0], False)
+        b = opened()
+        run(b, LARGE, True)
+        run(a, SHAPES[0], True)
+        a.close()
+        run(b, SHAPES[0], True)
+        b.close()
+        c = opened()
+        run(c, LARGE, True)
+    finally:
+        for d in open_handles:
+            d.close()
 
 
 def test_device_argument_errors(dev):

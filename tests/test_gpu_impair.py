@@ -76,6 +76,28 @@ def test_impair_device_in_place_sc16(dev, s0):
             assert np.array_equal(got, O.impair(SEED, 256 * 994, 0, iq, s0, 16)), (n, off)
 
 
+def test_table_lives_and_dies_with_the_handle():
+    """the noise table is uploaded when a handle opens and freed when it closes: a handle opened
+    after a close impairs from its own copy"""
+    d = G.Device(0)
+    try:
+        n, sigma, shift, s0 = SIZES[1][-1], SIGMAS[2], SHIFTS[1], STARTS[1]     # SC01, odd start
+        iq = samples(n, seed=n)
+        seed = (0x9E3779B97F4A7C15 * (s0 + 1) + sigma) & (2**64 - 1)
+        got = on_device(d, G.Impair(sigma, shift, seed), iq, s0, 1)
+        assert np.array_equal(got, O.impair(seed, sigma, shift, iq, s0, 1))
+    finally:
+        d.close()
+    d = G.Device(0)
+    try:
+        n, s0 = SIZES[16][-1], 2**32 - 5
+        iq = samples(n, seed=3)
+        got = on_device(d, G.Impair(256 * 994, 0, SEED), iq, s0, 16, in_place=True)
+        assert np.array_equal(got, O.impair(SEED, 256 * 994, 0, iq, s0, 16))
+    finally:
+        d.close()
+
+
 @pytest.mark.parametrize("fmt,in_off,out_off", [
     (16, 1, 4), (16, 3, 12), (16, 1, 8), (16, 0, 2),    # the last two never line up: edges only
     (8, 1, 2), (8, 3, 6), (8, 7, 14), (8, 1, 1),

@@ -177,6 +177,49 @@ def test_scratch_regrows(dev, monkeypatch):
     O.same_records(rec, count, wrec, wcount)
 
 
+def test_each_handle_owns_its_scratch(monkeypatch):
+    """Calls alternate between handles of one device, one job and 400, and go on after a handle
+    is closed and on a handle opened afterwards.  Every call leaves its state in its handle's own
+    state buffer, and in launches of 16 epochs the calls of 60 epochs continue from it: a buffer
+    shared between handles, or one that survived a close, would show in the records."""
+    set_path(monkeypatch, "fast", chunk=16)
+    fs, N, n_pull, jobs = O.SHAPES[0]
+    data, wrec, wcount = O.want(0, 16, 16)
+    trk = O.trk_of(fs, 16, O.gains_of(fs, n_pull))
+    mdata, mN, mjobs, gains, mrec, mcount = many_jobs()
+
+    def small(d):
+        rec, count = on_device(d, trk, data, N, O.jobs_array(jobs[:1]), wrec.shape[1])
+        O.same_records(rec, count, wrec[:1], wcount[:1])
+
+    def large(d):
+        rec, count = on_device(d, O.trk_of(64000, 16, gains), mdata, mN,
+                               O.jobs_array(mjobs + mjobs[:100]), mrec.shape[1])
+        O.same_records(rec, count, np.concatenate([mrec, mrec[:100]]),
+                       np.concatenate([mcount, mcount[:100]]))
+
+    open_handles = []
+
+    def opened():
+        open_handles.append(G.Device(0))
+        return open_handles[-1]
+
+    try:
+        a = opened()
+        small(a)
+        b = opened()
+        large(b)
+        small(a)
+        a.close()
+        small(b)
+        b.close()
+        c = opened()
+        large(c)
+    finally:
+        for d in open_handles:
+            d.close()
+
+
 def test_device_argument_errors(dev):
     import torch
     buf = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
