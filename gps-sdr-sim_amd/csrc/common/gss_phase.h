@@ -1165,6 +1165,11 @@ typedef struct gss_spec {              /* a row's speculative walk (GPU or host)
 } gss_spec_t;                          /* 16 + 32 GSS_SPEC_K bytes */
 #endif
 
+/* a row's segment count as every walk reads it: in->k clamped to 1..GSS_SPEC_K (0, segment starts
+   not guessed yet, walks as one segment) */
+GSS_HD int gss_spec_k_of(int k) { return k < 1 ? 1 : (k > GSS_SPEC_K ? GSS_SPEC_K : k); }
+GSS_HD int gss_spec_k(const gss_spec_in_t *in) { return gss_spec_k_of(in->k); }
+
 /* Exactly to the first wrap or n steps (the reference's order: ">= 1" before "< 0"). */
 GSS_HD int64_t gss_carr_to_wrap(double *x, double s, int64_t n, int *wr)
 {
@@ -1410,7 +1415,7 @@ GSS_HD void gss_spec_guess_row(double g, double s, int64_t n, gss_spec_in_t *in)
 GSS_HD void gss_spec_seg_walk(const gss_spec_in_t *in, int j, int64_t n, gss_spec_t *o)
 {
     const double s = in->s;
-    const int k = in->k < 1 ? 1 : (in->k > GSS_SPEC_K ? GSS_SPEC_K : in->k);
+    const int k = gss_spec_k(in);
     gss_spec_seg_t *sg = &o->seg[j];
     const int64_t stop = j + 1 < k ? in->P[j + 1] : n;
     double x;
@@ -1476,7 +1481,7 @@ GSS_HD double gss_spec_walk_rest(double v, int64_t pos, int64_t n, const gss_spe
 GSS_HD double gss_spec_fix_at(double v, int64_t n, const gss_spec_in_t *in, const gss_spec_t *o,
                               int *hit, double *dlast, double *av)
 {
-    const int k = in->k < 1 ? 1 : (in->k > GSS_SPEC_K ? GSS_SPEC_K : in->k);
+    const int k = gss_spec_k(in);
     int64_t pos = o->p1;
     double d = v - o->w1;                       /* exact: both on the post-wrap lattice */
     int j = 0;
@@ -1508,7 +1513,7 @@ GSS_HD double gss_spec_fix_d(double x, int64_t n, const gss_spec_in_t *in, const
                              int *hit, double *dlast, double *av)
 {
     const double s = in->s;
-    const int k = in->k < 1 ? 1 : (in->k > GSS_SPEC_K ? GSS_SPEC_K : in->k);
+    const int k = gss_spec_k(in);
     *hit = 0;
     double v = x;
     int wr = 0;
@@ -1535,7 +1540,7 @@ GSS_HD void gss_spec_anchors(double x, int64_t n, const gss_spec_in_t *in, const
     int hit = 0;
     double d = 0.0;
     (void)gss_spec_fix_d(x, n, in, o, &hit, &d, av);
-    const int k = in->k < 1 ? 1 : (in->k > GSS_SPEC_K ? GSS_SPEC_K : in->k);
+    const int k = gss_spec_k(in);
     pos[0] = 0;
     val[0] = x;
     for (int j = 1; j < GSS_SPEC_K; j++) {
@@ -1608,7 +1613,7 @@ typedef struct gss_spec_rec {          /* a row's speculative walk folded (GPU o
 GSS_HD int gss_spec_fold(const gss_spec_in_t *in, const gss_spec_t *o, double c, double lo,
                          double hi, double *olo, double *ohi, double *odd)
 {
-    const int k = in->k < 1 ? 1 : (in->k > GSS_SPEC_K ? GSS_SPEC_K : in->k);
+    const int k = gss_spec_k(in);
     for (int j = 0; j < k; j++) {
         const gss_spec_seg_t *sg = &o->seg[j];
         if (!(sg->dlo <= sg->dhi))
@@ -1649,6 +1654,8 @@ GSS_HD void gss_spec_record(const gss_spec_in_t *in, const gss_spec_t *o,
                             const gss_spec_in_t *pin, const gss_spec_t *po, int64_t n,
                             gss_spec_rec_t *r)
 {
+    /* (k and kp below keep the clamp written out: through gss_spec_k the record kernel's code
+       comes out different, profiles/refactor_chain) */
     const int k = in->k < 1 ? 1 : (in->k > GSS_SPEC_K ? GSS_SPEC_K : in->k);
     r->w1 = o->w1;
     r->p1 = (int32_t)(o->p1 < n ? o->p1 : n);

@@ -378,7 +378,7 @@ __global__ __launch_bounds__(64) void gss_spec_kernel(const gss_spec_in_t *in,
     if (lane < SPEC_ROWS)
         s_u.cc[lane].next = 0;
     __syncthreads();
-    const int kr = s_in[r].k, k = kr < 1 ? 1 : (kr > GSS_SPEC_K ? GSS_SPEC_K : kr);
+    const int kr = s_in[r].k, k = gss_spec_k_of(kr);
     const bool walk = live && j < kr;
     sc_res res;
     sc_seg_walk(g, s, s_in[r].P[j], s_in[r].W[j], j + 1 < k ? s_in[r].P[j + 1] : (int64_t)n, j,

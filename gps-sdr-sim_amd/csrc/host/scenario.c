@@ -6,10 +6,12 @@
  *   gss_scn_next  ≙ gpssim.c:2154-2188  (per-block refresh: range, code phase, gain)
  *                 + gpssim.c:2290-2352  (30 s nav/ephemeris/allocation update, time step)
  *                 + the carrier-phase chain the sample loop carries across blocks
- *                   (gpssim.c:2245-2250), produced exactly by the planner below.
+ *                   (gpssim.c:2245-2250): gss_carr_chain (carr_chain.c) over the batch's rows.
  *
- * The sample loop itself is not here: its inputs are emitted as gss_chan_blk_t rows and the
- * GPU synthesises them (gss_synth_*).
+ * Here: open, info, the 30 s updates, the rows of the next blocks, seek, the nav table, and a few
+ * small exported helpers.  The carrier chain and its speculative variants are carr_chain.c; they
+ * know no scenario.  The sample loop itself is not here either: its inputs are emitted as
+ * gss_chan_blk_t rows and the GPU synthesises them (gss_synth_*).
  */
 #include <math.h>
 #include <pthread.h>
@@ -398,601 +400,6 @@ int gss_scn_info(const gss_scn *s, gss_scn_info_t *info)
     info->next_block = s->iumd - 1;
     info->rows_out = s->rows_out;
     info->carrier_int = s->opt.carrier_int;
-    return 0;
-}
-
-/* ---- exact carrier planner ------------------------------------------------------------------
- * One chain per channel slot; a slot's chain restarts whenever allocateChannel re-initialises
- * its carr_phase.  Slots are independent, so the planner runs one slot per thread. */
-/* The integer carrier (FLOAT_CARR_PHASE undefined): carr_phase += carr_phasestep per sample in
-   a uint32 whose bits 16..24 index the LUT (gpssim.c:2202, 2252), i.e. a chain mod 2^25.  Rows
-   carry it as multiples of 2^-25 cycle; n steps from x is (x + n step) mod 1, exactly. */
-static double carr_int_walk(double x, double step, int n, double *ck)
-{
-    const uint32_t xi = (uint32_t)(x * K_CARR_INT_ONE);
-    const int64_t si = (int64_t)(step * K_CARR_INT_ONE);
-    if (ck)
-        for (int j = 0; j < GSS_NCK; j++)
-            ck[j] = (double)((xi + (uint32_t)(si * gss_ck_pos(j, n))) & 0x1FFFFFFu) /
-                    K_CARR_INT_ONE;
-    return (double)((xi + (uint32_t)(si * n)) & 0x1FFFFFFu) / K_CARR_INT_ONE;
-}
-
-typedef struct {
-    double *carr;
-    gss_chan_blk_t *blk;
-    const int32_t *nch;
-    const gss_chain_t *chain;
-    double *ck;
-    int nblk, n_per_blk, carrier_int, slot_lo, slot_hi;
-} plan_job;
-
-static void *plan_slots(void *arg)
-{
-    plan_job *j = arg;
-    for (int slot = j->slot_lo; slot < j->slot_hi; slot++) {
-        double x = j->carr[slot];
-        for (int b = 0; b < j->nblk; b++) {
-            for (int k = 0; k < j->nch[b]; k++) {
-                size_t e = (size_t)b * GSS_MAXCH + k;
-                if (j->chain[e].slot != slot)
-                    continue;
-                if (j->chain[e].reset)
-                    x = j->chain[e].init;
-                j->blk[e].carr0 = x;
-                if (j->carrier_int)        /* exact integer chain, checkpoints included */
-                    x = carr_int_walk(x, j->blk[e].carr_step, j->n_per_blk,
-                                      j->ck ? j->ck + e * GSS_NCK : NULL);
-                else if (j->ck) /* same walk, recording the sub-block checkpoints on the way */
-                    x = gss_carr_walk_ck(x, j->blk[e].carr_step, j->n_per_blk,
-                                         j->ck + e * GSS_NCK);
-                else
-                    x = gss_carr_walk_cc(x, j->blk[e].carr_step, j->n_per_blk);
-                break;
-            }
-        }
-        j->carr[slot] = x;
-    }
-    return NULL;
-}
-
-static void plan_slot_part(void *arg, int slot)
-{
-    plan_job j = *(const plan_job *)arg;
-    j.slot_lo = slot;
-    j.slot_hi = slot + 1;
-    (void)plan_slots(&j);
-}
-
-/* The carrier chain (gpssim.c:2245-2250, carried across blocks) over nblk consecutive blocks:
-   one chain per channel slot, restarted where allocateChannel re-initialised it; slots are
-   independent, so one slot per thread. */
-int gss_carr_chain(double *carr, gss_chan_blk_t *blk, const int32_t *nch,
-                   const gss_chain_t *chain, int nblk, int n_per_blk, int carrier_int,
-                   double *carr_ck, int threads)
-{
-    if (carr == NULL || (nblk > 0 && (blk == NULL || nch == NULL || chain == NULL)) ||
-        nblk < 0 || n_per_blk <= 0)
-        return gss_fail(GSS_E_ARG, "invalid carrier-chain arguments");
-    const plan_job all = {carr, blk, nch, chain, carr_ck, nblk, n_per_blk, carrier_int, 0,
-                          K_MAX_CHAN};
-    gss_pool_run(threads, K_MAX_CHAN, plan_slot_part, (void *)&all);   /* one part per slot */
-    return 0;
-}
-
-/* ---- the chain with the block walks run ahead (gss_phase.h, speculative block walk) ---------- */
-typedef struct {
-    const gss_chan_blk_t *blk;
-    int n_per_blk;
-    gss_spec_in_t *in;
-} guess_job;
-
-static void guess_part(void *arg, int b)
-{
-    const guess_job *j = arg;
-    for (int k = 0; k < GSS_MAXCH; k++) {
-        gss_spec_in_t *r = &j->in[(size_t)b * GSS_MAXCH + k];
-        if (r->k == 0)
-            gss_spec_guess_row(r->g, r->s, j->n_per_blk, r);
-    }
-}
-
-/* the starts, serially: the line of each slot from its exact start (in double: the drift over a
-   batch, ~1e-13 per block, stays far inside the translation intervals); k = 0 on live rows (their
-   segment starts not guessed yet), 1 on padding rows; pad = the index of the previous row of the
-   same slot chain in the batch (-1: the slot's first row here, or a re-initialisation), which the
-   records' links read (gss_spec_records*) */
-static void chain_starts(const double *carr, const gss_chan_blk_t *blk, const int32_t *nch,
-                         const gss_chain_t *chain, int nblk, int n_per_blk, gss_spec_in_t *in)
-{
-    double run[K_MAX_CHAN];
-    int32_t last[K_MAX_CHAN];
-    for (int i = 0; i < K_MAX_CHAN; i++) {
-        run[i] = carr[i];
-        last[i] = -1;
-    }
-    for (int b = 0; b < nblk; b++)
-        for (int k = 0; k < GSS_MAXCH; k++) {
-            const size_t e = (size_t)b * GSS_MAXCH + k;
-            const int slot = k < nch[b] ? chain[e].slot : -1;
-            in[e].k = 1;
-            in[e].pad = -1;
-            in[e].s = 0.0;
-            in[e].g = 0.0;
-            if (slot < 0 || slot >= K_MAX_CHAN)
-                continue;
-            if (chain[e].reset) {
-                run[slot] = chain[e].init;
-                last[slot] = -1;
-            }
-            in[e].pad = last[slot];
-            last[slot] = (int32_t)e;
-            const double g = run[slot];
-            in[e].g = g >= 0.0 && g < 1.0 ? g : 0.0;
-            in[e].s = blk[e].carr_step;
-            in[e].k = 0;
-            const double v = g + (double)n_per_blk * blk[e].carr_step;
-            run[slot] = v - floor(v);
-        }
-}
-
-/* The slots' carriers after the batch, predicted by the same lines (a start for the batch after
-   it while its own chain is still pending: ~3e-10 cycle off after 2,048 blocks, far inside the
-   translation intervals) */
-int gss_carr_line_end(const double *carr, const gss_chan_blk_t *blk, const int32_t *nch,
-                      const gss_chain_t *chain, int nblk, int n_per_blk, double *carr_end)
-{
-    if (carr == NULL || carr_end == NULL || nblk < 0 || n_per_blk <= 0 ||
-        (nblk > 0 && (blk == NULL || nch == NULL || chain == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid carrier-line arguments");
-    double run[K_MAX_CHAN];
-    for (int i = 0; i < K_MAX_CHAN; i++)
-        run[i] = carr[i];
-    for (int b = 0; b < nblk; b++)
-        for (int k = 0; k < nch[b] && k < GSS_MAXCH; k++) {
-            const size_t e = (size_t)b * GSS_MAXCH + k;
-            const int slot = chain[e].slot;
-            if (slot < 0 || slot >= K_MAX_CHAN)
-                continue;
-            if (chain[e].reset)
-                run[slot] = chain[e].init;
-            const double v = run[slot] + (double)n_per_blk * blk[e].carr_step;
-            run[slot] = v - floor(v);
-        }
-    for (int i = 0; i < K_MAX_CHAN; i++)
-        carr_end[i] = run[i];
-    return 0;
-}
-
-int gss_carr_chain_starts(const double *carr, const gss_chan_blk_t *blk, const int32_t *nch,
-                          const gss_chain_t *chain, int nblk, int n_per_blk, gss_spec_in_t *in)
-{
-    if (carr == NULL || in == NULL || nblk < 0 || n_per_blk <= 0 ||
-        (nblk > 0 && (blk == NULL || nch == NULL || chain == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid carrier-guess arguments");
-    chain_starts(carr, blk, nch, chain, nblk, n_per_blk, in);
-    return 0;
-}
-
-int gss_carr_chain_guess(const double *carr, const gss_chan_blk_t *blk, const int32_t *nch,
-                         const gss_chain_t *chain, int nblk, int n_per_blk, gss_spec_in_t *in)
-{
-    if (carr == NULL || in == NULL || nblk < 0 || n_per_blk <= 0 ||
-        (nblk > 0 && (blk == NULL || nch == NULL || chain == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid carrier-guess arguments");
-    chain_starts(carr, blk, nch, chain, nblk, n_per_blk, in);
-    /* the segment starts, in parallel over blocks */
-    const guess_job j = {blk, n_per_blk, in};
-    gss_pool_run(8, nblk, guess_part, (void *)&j);
-    return 0;
-}
-
-typedef struct {
-    gss_spec_in_t *in;
-    int nrow, n_per_blk;
-    gss_spec_t *spec;
-} spec_host_job;
-
-static void spec_host_part(void *arg, int part)
-{
-    const spec_host_job *j = arg;
-    for (int i = part * 16; i < j->nrow && i < part * 16 + 16; i++) {
-        if (j->in[i].k == 0)                     /* segment starts not guessed yet */
-            gss_spec_guess_row(j->in[i].g, j->in[i].s, j->n_per_blk, &j->in[i]);
-        for (int g = 0; g < j->in[i].k && g < GSS_SPEC_K; g++)
-            gss_spec_seg_walk(&j->in[i], g, j->n_per_blk, &j->spec[i]);
-    }
-}
-
-int gss_spec_host(gss_spec_in_t *in, int nrow, int n_per_blk, gss_spec_t *spec, int threads)
-{
-    if (nrow < 0 || n_per_blk <= 0 || (nrow > 0 && (in == NULL || spec == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid speculative-walk arguments");
-    const spec_host_job j = {in, nrow, n_per_blk, spec};
-    gss_pool_run(threads, (nrow + 15) / 16, spec_host_part, (void *)&j);
-    return 0;
-}
-
-typedef struct {
-    double *carr;
-    gss_chan_blk_t *blk;
-    const int32_t *nch;
-    const gss_chain_t *chain;
-    const gss_spec_in_t *in;
-    const gss_spec_t *spec;
-    gss_carr_anchor_t *anch;
-    int nblk, n_per_blk;
-    int hits[K_MAX_CHAN];
-} spec_chain_job;
-
-/* one row's end from its true start x; with a != NULL its anchors: the start, and the exact value
-   at every segment start the fix-up passed or walked */
-static double fix_row(double x, int n, const gss_spec_in_t *in, const gss_spec_t *o, int *hit,
-                      double *d, gss_carr_anchor_t *a)
-{
-    if (a == NULL)
-        return gss_spec_fix_d(x, n, in, o, hit, d, NULL);
-    double av[GSS_SPEC_K];
-    for (int j = 0; j < GSS_SPEC_K; j++)
-        av[j] = -1.0;                                /* a carrier value is never negative */
-    const double end = gss_spec_fix_d(x, n, in, o, hit, d, av);
-    const int k = in->k < 1 ? 1 : (in->k > GSS_SPEC_K ? GSS_SPEC_K : in->k);
-    a->pos[0] = 0;
-    a->val[0] = x;
-    for (int j = 1; j < GSS_SPEC_K; j++) {
-        const int ok = j < k && av[j] >= 0.0 && in->P[j] > 0 && in->P[j] < n;
-        a->pos[j] = ok ? (int32_t)in->P[j] : -1;
-        a->val[j] = ok ? av[j] : 0.0;
-    }
-    return end;
-}
-
-static void spec_slot_part(void *arg, int slot)
-{
-    spec_chain_job *j = arg;
-    double x = j->carr[slot], d = 0.0;
-    int hits = 0;
-    for (int b = 0; b < j->nblk; b++)
-        for (int k = 0; k < j->nch[b]; k++) {
-            const size_t e = (size_t)b * GSS_MAXCH + k;
-            if (j->chain[e].slot != slot)
-                continue;
-            if (j->chain[e].reset)
-                x = j->chain[e].init;
-            j->blk[e].carr0 = x;
-            int hit = 0;
-            x = fix_row(x, j->n_per_blk, &j->in[e], &j->spec[e], &hit, &d,
-                        j->anch ? &j->anch[e] : NULL);
-            hits += hit;
-            break;
-        }
-    j->carr[slot] = x;
-    j->hits[slot] = hits;
-}
-
-static void anchors_none(gss_carr_anchor_t *anch, const int32_t *nch, int nblk)
-{
-    for (int b = 0; b < nblk; b++)
-        for (int k = 0; k < GSS_MAXCH; k++) {
-            gss_carr_anchor_t *a = &anch[(size_t)b * GSS_MAXCH + k];
-            for (int j = 0; j < GSS_SPEC_K; j++) {
-                a->pos[j] = -1;
-                a->val[j] = 0.0;
-            }
-        }
-    (void)nch;
-}
-
-int gss_carr_chain_anchored(double *carr, gss_chan_blk_t *blk, const int32_t *nch,
-                            const gss_chain_t *chain, int nblk, int n_per_blk,
-                            const gss_spec_in_t *in, const gss_spec_t *spec, int threads,
-                            int *n_hit, gss_carr_anchor_t *anch)
-{
-    if (carr == NULL || nblk < 0 || n_per_blk <= 0 ||
-        (nblk > 0 && (blk == NULL || nch == NULL || chain == NULL || in == NULL || spec == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid carrier-chain arguments");
-    if (anch)
-        anchors_none(anch, nch, nblk);                /* padding rows: none */
-    spec_chain_job j = {carr, blk, nch, chain, in, spec, anch, nblk, n_per_blk, {0}};
-    gss_pool_run(threads, K_MAX_CHAN, spec_slot_part, (void *)&j);   /* one part per slot */
-    if (n_hit) {
-        int h = 0;
-        for (int i = 0; i < K_MAX_CHAN; i++)
-            h += j.hits[i];
-        *n_hit = h;
-    }
-    return 0;
-}
-
-int gss_carr_chain_spec(double *carr, gss_chan_blk_t *blk, const int32_t *nch,
-                        const gss_chain_t *chain, int nblk, int n_per_blk,
-                        const gss_spec_in_t *in, const gss_spec_t *spec, int threads,
-                        int *n_hit)
-{
-    return gss_carr_chain_anchored(carr, blk, nch, chain, nblk, n_per_blk, in, spec, threads,
-                                   n_hit, NULL);
-}
-
-/* anchors of rows whose carr0 the chain has set (any chain): in parallel over blocks */
-typedef struct {
-    const gss_chan_blk_t *blk;
-    const int32_t *nch;
-    const gss_spec_in_t *in;
-    const gss_spec_t *spec;
-    gss_carr_anchor_t *anch;
-    int n_per_blk;
-} anchor_job;
-
-static void anchor_part(void *arg, int b)
-{
-    const anchor_job *j = arg;
-    for (int k = 0; k < j->nch[b] && k < GSS_MAXCH; k++) {
-        const size_t e = (size_t)b * GSS_MAXCH + k;
-        gss_spec_anchors(j->blk[e].carr0, j->n_per_blk, &j->in[e], &j->spec[e],
-                         j->anch[e].pos, j->anch[e].val);
-    }
-}
-
-int gss_carr_anchors(const gss_chan_blk_t *blk, const int32_t *nch, int nblk, int n_per_blk,
-                     const gss_spec_in_t *in, const gss_spec_t *spec, gss_carr_anchor_t *anch,
-                     int threads)
-{
-    if (nblk < 0 || n_per_blk <= 0 ||
-        (nblk > 0 && (blk == NULL || nch == NULL || in == NULL || spec == NULL || anch == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid carrier-anchor arguments");
-    anchors_none(anch, nch, nblk);
-    const anchor_job j = {blk, nch, in, spec, anch, n_per_blk};
-    gss_pool_run(threads, nblk, anchor_part, (void *)&j);
-    return 0;
-}
-
-/* ---- links between a slot's consecutive rows (gss_spec_links / gss_carr_chain_linked) --------
- * Where row e' of a slot translated by d (its end = its last segment's end + d), the next row e of
- * the slot starts at y + d, y = that segment's end: known before the chain runs.  So e's partial
- * cycle to its first wrap is walked from y ahead of time with the admissible translations of y,
- * and e's whole walk folds into one record: e translates iff d is in [lo, hi], and then its own
- * last translation is d + dd and its end is end + (d + dd).  Exact: every translation the record
- * chains (d_0 = d + (w1' - w1), d_j+1 = d_j + (end_j - W_j+1)) is a sum of post-wrap lattice
- * values (multiples of 2^-52 ascending, 2^-53 descending, below 2 in magnitude), so the double
- * arithmetic carries it exactly, and the bounds lo_j - c_j are rounded inward. */
-typedef struct {
-    const int32_t *nch;
-    const gss_chain_t *chain;
-    const gss_spec_in_t *in;
-    const gss_spec_t *spec;
-    gss_spec_link_t *link;
-    int nblk, n_per_blk;
-} link_job;
-
-/* the record of row e entered from y (the previous row's last segment end); 0: none */
-static int link_row(double y, const gss_spec_in_t *in, const gss_spec_t *o, int64_t n,
-                    gss_spec_link_t *L)
-{
-    double lo, hi, dd;
-    if (!gss_spec_link_fold(y, in, o, n, &lo, &hi, &dd))
-        return 0;
-    L->lo = lo;
-    L->hi = hi;
-    L->dd = dd;
-    const int k = in->k < 1 ? 1 : (in->k > GSS_SPEC_K ? GSS_SPEC_K : in->k);
-    L->end = o->seg[k - 1].end;
-    return 1;
-}
-
-static void link_slot_part(void *arg, int slot)
-{
-    const link_job *j = arg;
-    int64_t prev = -1;
-    for (int b = 0; b < j->nblk; b++)
-        for (int k = 0; k < j->nch[b]; k++) {
-            const size_t e = (size_t)b * GSS_MAXCH + k;
-            if (j->chain[e].slot != slot)
-                continue;
-            gss_spec_link_t *L = &j->link[e];
-            L->lo = 1.0;                          /* an empty interval: no record */
-            L->hi = 0.0;
-            L->dd = L->end = 0.0;
-            if (prev >= 0 && !j->chain[e].reset && j->in[e].s != 0.0 && j->in[prev].s != 0.0) {
-                const gss_spec_in_t *pi = &j->in[prev];
-                const int kp = pi->k < 1 ? 1 : (pi->k > GSS_SPEC_K ? GSS_SPEC_K : pi->k);
-                if (!link_row(j->spec[prev].seg[kp - 1].end, &j->in[e], &j->spec[e],
-                              j->n_per_blk, L)) {
-                    L->lo = 1.0;
-                    L->hi = 0.0;
-                }
-            }
-            prev = (int64_t)e;
-            break;
-        }
-}
-
-int gss_spec_links(const int32_t *nch, const gss_chain_t *chain, int nblk, int n_per_blk,
-                   const gss_spec_in_t *in, const gss_spec_t *spec, gss_spec_link_t *link,
-                   int threads)
-{
-    if (nblk < 0 || n_per_blk <= 0 ||
-        (nblk > 0 && (nch == NULL || chain == NULL || in == NULL || spec == NULL || link == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid spec-link arguments");
-    for (size_t e = 0; e < (size_t)nblk * GSS_MAXCH; e++) {
-        link[e].lo = 1.0;
-        link[e].hi = 0.0;
-        link[e].dd = link[e].end = 0.0;
-    }
-    const link_job j = {nch, chain, in, spec, link, nblk, n_per_blk};
-    gss_pool_run(threads, K_MAX_CHAN, link_slot_part, (void *)&j);      /* one part per slot */
-    return 0;
-}
-
-typedef struct {
-    double *carr;
-    gss_chan_blk_t *blk;
-    const int32_t *nch;
-    const gss_chain_t *chain;
-    const gss_spec_in_t *in;
-    const gss_spec_t *spec;
-    const gss_spec_link_t *link;
-    int nblk, n_per_blk;
-    int hits[K_MAX_CHAN];
-} linked_job;
-
-static void linked_slot_part(void *arg, int slot)
-{
-    linked_job *j = arg;
-    double x = j->carr[slot], d = 0.0;
-    int hits = 0, held = 0;
-    for (int b = 0; b < j->nblk; b++)
-        for (int k = 0; k < j->nch[b]; k++) {
-            const size_t e = (size_t)b * GSS_MAXCH + k;
-            if (j->chain[e].slot != slot)
-                continue;
-            if (j->chain[e].reset) {
-                x = j->chain[e].init;
-                held = 0;
-            }
-            j->blk[e].carr0 = x;
-            const gss_spec_link_t *L = &j->link[e];
-            int hit = 0;
-            if (held && d >= L->lo && d <= L->hi) {
-                d += L->dd;
-                x = L->end + d;
-                hit = 1;
-            } else {
-                x = gss_spec_fix_d(x, j->n_per_blk, &j->in[e], &j->spec[e], &hit, &d, NULL);
-            }
-            held = hit;
-            hits += hit;
-            break;
-        }
-    j->carr[slot] = x;
-    j->hits[slot] = hits;
-}
-
-int gss_carr_chain_linked(double *carr, gss_chan_blk_t *blk, const int32_t *nch,
-                          const gss_chain_t *chain, int nblk, int n_per_blk,
-                          const gss_spec_in_t *in, const gss_spec_t *spec,
-                          const gss_spec_link_t *link, int threads, int *n_hit)
-{
-    if (carr == NULL || nblk < 0 || n_per_blk <= 0 ||
-        (nblk > 0 && (blk == NULL || nch == NULL || chain == NULL || in == NULL || spec == NULL ||
-                      link == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid carrier-chain arguments");
-    linked_job j = {carr, blk, nch, chain, in, spec, link, nblk, n_per_blk, {0}};
-    gss_pool_run(threads, K_MAX_CHAN, linked_slot_part, (void *)&j);
-    if (n_hit) {
-        int h = 0;
-        for (int i = 0; i < K_MAX_CHAN; i++)
-            h += j.hits[i];
-        *n_hit = h;
-    }
-    return 0;
-}
-
-/* ---- records: each row's walk folded (gss_phase.h gss_spec_record), the chain from them ------- */
-typedef struct {
-    const gss_spec_in_t *in;
-    const gss_spec_t *spec;
-    gss_spec_rec_t *rec;
-    int nrow, n_per_blk;
-} rec_job;
-
-static void rec_part(void *arg, int part)
-{
-    const rec_job *j = arg;
-    for (int i = part * 64; i < j->nrow && i < part * 64 + 64; i++) {
-        const int p = j->in[i].pad;
-        const int ok = p >= 0 && p < i;
-        gss_spec_record(&j->in[i], &j->spec[i], ok ? &j->in[p] : NULL, ok ? &j->spec[p] : NULL,
-                        j->n_per_blk, &j->rec[i]);
-        if (j->rec[i].ok & 2)
-            j->rec[i].ok |= (i - p) << 2;            /* the row the link was built against */
-    }
-}
-
-int gss_spec_records(const gss_spec_in_t *in, const gss_spec_t *spec, int nrow, int n_per_blk,
-                     gss_spec_rec_t *rec, int threads)
-{
-    if (nrow < 0 || n_per_blk <= 0 || (nrow > 0 && (in == NULL || spec == NULL || rec == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid spec-record arguments");
-    const rec_job j = {in, spec, rec, nrow, n_per_blk};
-    gss_pool_run(threads, (nrow + 63) / 64, rec_part, (void *)&j);
-    return 0;
-}
-
-typedef struct {
-    double *carr;
-    gss_chan_blk_t *blk;
-    const int32_t *nch;
-    const gss_chain_t *chain;
-    const gss_spec_rec_t *rec;
-    int nblk, n_per_blk;
-    int hits[K_MAX_CHAN];
-} rec_chain_job;
-
-static void rec_slot_part(void *arg, int slot)
-{
-    rec_chain_job *j = arg;
-    const int64_t n = j->n_per_blk;
-    double x = j->carr[slot], d = 0.0;
-    int hits = 0, held = 0;
-    size_t e_prev = 0;                               /* the slot's previous row (held: valid) */
-    for (int b = 0; b < j->nblk; b++)
-        for (int k = 0; k < j->nch[b]; k++) {
-            const size_t e = (size_t)b * GSS_MAXCH + k;
-            if (j->chain[e].slot != slot)
-                continue;
-            if (j->chain[e].reset) {
-                x = j->chain[e].init;
-                held = 0;
-            }
-            j->blk[e].carr0 = x;
-            const gss_spec_rec_t *R = &j->rec[e];
-            /* a link record holds only if it was built against this slot's previous row
-               (ok bits 2.., the row distance; rows from elsewhere, e.g. zero-filled pads, fail
-               the check and walk) */
-            const int linked = held && (R->ok & 2) && (size_t)(R->ok >> 2) == e - e_prev;
-            e_prev = e;
-            if (linked && d >= R->llo && d <= R->lhi) {
-                d += R->ldd;                         /* the link: no walk at all */
-                x = R->end + d;
-                hits++;
-                break;
-            }
-            const double s = j->blk[e].carr_step;
-            double v = x;
-            int wr = 0;
-            const int64_t t = gss_carr_to_wrap(&v, s, n, &wr);
-            held = 0;
-            if (!wr || t >= n) {
-                x = v;                               /* no wrap: walked exactly */
-            } else if ((R->ok & 1) && t == R->p1 && v - R->w1 >= R->slo && v - R->w1 <= R->shi) {
-                d = (v - R->w1) + R->sdd;            /* the row's own record */
-                x = R->end + d;
-                held = 1;
-                hits++;
-            } else {
-                x = gss_carr_walk_cc(v, s, n - t);   /* a translation fails: the exact walk */
-            }
-            break;
-        }
-    j->carr[slot] = x;
-    j->hits[slot] = hits;
-}
-
-int gss_carr_chain_records(double *carr, gss_chan_blk_t *blk, const int32_t *nch,
-                           const gss_chain_t *chain, int nblk, int n_per_blk,
-                           const gss_spec_rec_t *rec, int threads, int *n_hit)
-{
-    if (carr == NULL || nblk < 0 || n_per_blk <= 0 ||
-        (nblk > 0 && (blk == NULL || nch == NULL || chain == NULL || rec == NULL)))
-        return gss_fail(GSS_E_ARG, "invalid carrier-chain arguments");
-    rec_chain_job j = {carr, blk, nch, chain, rec, nblk, n_per_blk, {0}};
-    gss_pool_run(threads, K_MAX_CHAN, rec_slot_part, (void *)&j);
-    if (n_hit) {
-        int h = 0;
-        for (int i = 0; i < K_MAX_CHAN; i++)
-            h += j.hits[i];
-        *n_hit = h;
-    }
     return 0;
 }
 
@@ -1437,16 +844,6 @@ int gss_ca_table(uint32_t *out)
         ca_pack(ca, out + (size_t)(prn - 1) * GSS_CA_WORDS);
     }
     return 0;
-}
-
-double gss_carr_advance(double carr, double step, int64_t n)
-{
-    return gss_carr_walk_cc(carr, step, n);
-}
-
-double gss_carr_advance_ck(double carr, double step, int n, double *ck)
-{
-    return gss_carr_walk_ck(carr, step, n, ck);
 }
 
 double gss_code_advance(double code, double step, int64_t n, int32_t *icode, int32_t *ibit,

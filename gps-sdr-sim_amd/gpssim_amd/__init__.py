@@ -737,14 +737,30 @@ class Scenario:
             pass
 
 
+def _chain_args(carr, blk, nch, chain, fill=True):
+    """The chain calls' shared arguments as (carr, blk, nch, chain), contiguous and typed.  fill:
+    the call advances carr[16] (a copy) and writes carr0 into blk itself, which must then be a
+    contiguous CHAN_DTYPE array already."""
+    if fill:
+        c = np.array(carr, np.float64, copy=True)
+        assert c.shape == (MAXCH,) and blk.flags.c_contiguous and blk.dtype == CHAN_DTYPE
+    else:
+        c, blk = np.ascontiguousarray(carr, np.float64), np.ascontiguousarray(blk)
+    return c, blk, np.ascontiguousarray(nch, np.int32), np.ascontiguousarray(chain, CHAIN_DTYPE)
+
+
+def _rows(a, dtype, n=None):
+    """Per-row records (guesses, walks, links, records) as a contiguous array of n rows."""
+    a = np.ascontiguousarray(a, dtype)
+    assert n is None or a.size == n
+    return a
+
+
 def carr_chain(carr, blk, nch, chain, n_per_blk, carrier_int=False, with_ck=True, threads=8):
     """The carrier chain over deferred rows (gss_carr_chain): fills blk["carr0"] in place from
     carr[16] = the slot carriers at the first block; returns (carrier after the last block,
     checkpoints [nb, 16, NCK] or None)."""
-    c = np.array(carr, np.float64, copy=True)
-    assert c.shape == (MAXCH,) and blk.flags.c_contiguous and blk.dtype == CHAN_DTYPE
-    nch = np.ascontiguousarray(nch, np.int32)
-    chain = np.ascontiguousarray(chain, CHAIN_DTYPE)
+    c, blk, nch, chain = _chain_args(carr, blk, nch, chain)
     nb = len(nch)
     ck = np.zeros((nb, MAXCH, NCK), np.float64) if with_ck else None
     _check(lib().gss_carr_chain(_ptr(c), _ptr(blk), _ptr(nch), _ptr(chain), nb, int(n_per_blk),
@@ -755,23 +771,18 @@ def carr_chain(carr, blk, nch, chain, n_per_blk, carrier_int=False, with_ck=True
 def carr_chain_guess(carr, blk, nch, chain, n_per_blk, starts_only=False):
     """Each row's guesses (gss_carr_chain_guess): SPEC_IN_DTYPE [nb, 16].  starts_only: the
     starts alone (gss_carr_chain_starts), live rows with k = 0 for the walkers to complete."""
-    c = np.ascontiguousarray(carr, np.float64)
-    nch = np.ascontiguousarray(nch, np.int32)
-    chain = np.ascontiguousarray(chain, CHAIN_DTYPE)
+    c, blk, nch, chain = _chain_args(carr, blk, nch, chain, fill=False)
     gi = np.zeros((len(nch), MAXCH), SPEC_IN_DTYPE)
     fn = lib().gss_carr_chain_starts if starts_only else lib().gss_carr_chain_guess
-    _check(fn(_ptr(c), _ptr(np.ascontiguousarray(blk)), _ptr(nch), _ptr(chain), len(nch),
-              int(n_per_blk), _ptr(gi)))
+    _check(fn(_ptr(c), _ptr(blk), _ptr(nch), _ptr(chain), len(nch), int(n_per_blk), _ptr(gi)))
     return gi
 
 
 def carr_line_end(carr, blk, nch, chain, n_per_blk):
     """The slots' carriers after the batch by the lines of gss_carr_chain_starts (a prediction)."""
-    c = np.ascontiguousarray(carr, np.float64)
+    c, blk, nch, chain = _chain_args(carr, blk, nch, chain, fill=False)
     out = np.zeros(MAXCH, np.float64)
-    nch = np.ascontiguousarray(nch, np.int32)
-    _check(lib().gss_carr_line_end(_ptr(c), _ptr(np.ascontiguousarray(blk)), _ptr(nch),
-                                   _ptr(np.ascontiguousarray(chain, CHAIN_DTYPE)), len(nch),
+    _check(lib().gss_carr_line_end(_ptr(c), _ptr(blk), _ptr(nch), _ptr(chain), len(nch),
                                    int(n_per_blk), _ptr(out)))
     return out
 
@@ -779,7 +790,7 @@ def carr_line_end(carr, blk, nch, chain, n_per_blk):
 def spec_host(gi, n_per_blk, threads=8):
     """The speculative walk of every row's segments (gss_spec_host): SPEC_DTYPE rows.  Rows with
     k = 0 get their segment guesses first, written back into gi (a contiguous array)."""
-    gi = np.ascontiguousarray(gi, SPEC_IN_DTYPE).reshape(-1)
+    gi = _rows(gi, SPEC_IN_DTYPE).reshape(-1)
     spec = np.zeros(len(gi), SPEC_DTYPE)
     _check(lib().gss_spec_host(_ptr(gi), len(gi), int(n_per_blk), _ptr(spec), threads))
     return spec
@@ -789,13 +800,9 @@ def carr_chain_spec(carr, blk, nch, chain, n_per_blk, gi, spec, threads=8):
     """The carrier chain from the rows' speculative walks (gss_carr_chain_spec): fills
     blk["carr0"] in place; returns (carrier after the last block, blocks where the translation
     carried through)."""
-    c = np.array(carr, np.float64, copy=True)
-    assert c.shape == (MAXCH,) and blk.flags.c_contiguous and blk.dtype == CHAN_DTYPE
-    nch = np.ascontiguousarray(nch, np.int32)
-    chain = np.ascontiguousarray(chain, CHAIN_DTYPE)
-    gi = np.ascontiguousarray(gi, SPEC_IN_DTYPE)
-    spec = np.ascontiguousarray(spec, SPEC_DTYPE)
-    assert spec.size == gi.size == len(nch) * MAXCH
+    c, blk, nch, chain = _chain_args(carr, blk, nch, chain)
+    n = len(nch) * MAXCH
+    gi, spec = _rows(gi, SPEC_IN_DTYPE, n), _rows(spec, SPEC_DTYPE, n)
     hit = C.c_int(0)
     _check(lib().gss_carr_chain_spec(_ptr(c), _ptr(blk), _ptr(nch), _ptr(chain), len(nch),
                                      int(n_per_blk), _ptr(gi), _ptr(spec), threads,
@@ -806,13 +813,9 @@ def carr_chain_spec(carr, blk, nch, chain, n_per_blk, gi, spec, threads=8):
 def carr_chain_anchored(carr, blk, nch, chain, n_per_blk, gi, spec, threads=8):
     """carr_chain_spec, also returning the chain's anchors (gss_carr_chain_anchored):
     (end carriers, hits, ANCHOR_DTYPE [nb, 16])."""
-    c = np.array(carr, np.float64, copy=True)
-    assert c.shape == (MAXCH,) and blk.flags.c_contiguous and blk.dtype == CHAN_DTYPE
-    nch = np.ascontiguousarray(nch, np.int32)
-    chain = np.ascontiguousarray(chain, CHAIN_DTYPE)
-    gi = np.ascontiguousarray(gi, SPEC_IN_DTYPE)
-    spec = np.ascontiguousarray(spec, SPEC_DTYPE)
-    assert spec.size == gi.size == len(nch) * MAXCH
+    c, blk, nch, chain = _chain_args(carr, blk, nch, chain)
+    n = len(nch) * MAXCH
+    gi, spec = _rows(gi, SPEC_IN_DTYPE, n), _rows(spec, SPEC_DTYPE, n)
     anch = np.zeros((len(nch), MAXCH), ANCHOR_DTYPE)
     hit = C.c_int(0)
     _check(lib().gss_carr_chain_anchored(_ptr(c), _ptr(blk), _ptr(nch), _ptr(chain), len(nch),
@@ -825,9 +828,8 @@ def carr_anchors(blk, nch, n_per_blk, gi, spec, threads=8):
     """The anchors of rows whose carr0 a chain has set (gss_carr_anchors): ANCHOR_DTYPE [nb, 16]."""
     blk = np.ascontiguousarray(blk, CHAN_DTYPE)
     nch = np.ascontiguousarray(nch, np.int32)
-    gi = np.ascontiguousarray(gi, SPEC_IN_DTYPE)
-    spec = np.ascontiguousarray(spec, SPEC_DTYPE)
-    assert spec.size == gi.size == len(nch) * MAXCH
+    n = len(nch) * MAXCH
+    gi, spec = _rows(gi, SPEC_IN_DTYPE, n), _rows(spec, SPEC_DTYPE, n)
     anch = np.zeros((len(nch), MAXCH), ANCHOR_DTYPE)
     _check(lib().gss_carr_anchors(_ptr(blk), _ptr(nch), len(nch), int(n_per_blk), _ptr(gi),
                                   _ptr(spec), _ptr(anch), threads))
@@ -837,9 +839,8 @@ def carr_anchors(blk, nch, n_per_blk, gi, spec, threads=8):
 def spec_records(gi, spec, n_per_blk, threads=8):
     """Each row's record (gss_spec_records; the previous row of its slot from gi["pad"]):
     SPEC_REC_DTYPE rows shaped like gi."""
-    gi = np.ascontiguousarray(gi, SPEC_IN_DTYPE)
-    spec = np.ascontiguousarray(spec, SPEC_DTYPE)
-    assert spec.size == gi.size
+    gi = _rows(gi, SPEC_IN_DTYPE)
+    spec = _rows(spec, SPEC_DTYPE, gi.size)
     rec = np.zeros(gi.shape, SPEC_REC_DTYPE)
     _check(lib().gss_spec_records(_ptr(gi), _ptr(spec), gi.size, int(n_per_blk), _ptr(rec),
                                   threads))
@@ -849,12 +850,8 @@ def spec_records(gi, spec, n_per_blk, threads=8):
 def carr_chain_records(carr, blk, nch, chain, n_per_blk, rec, threads=8):
     """The chain from the rows' records (gss_carr_chain_records): fills blk["carr0"] in place;
     returns (carrier after the last block, rows whose record held)."""
-    c = np.array(carr, np.float64, copy=True)
-    assert c.shape == (MAXCH,) and blk.flags.c_contiguous and blk.dtype == CHAN_DTYPE
-    nch = np.ascontiguousarray(nch, np.int32)
-    chain = np.ascontiguousarray(chain, CHAIN_DTYPE)
-    rec = np.ascontiguousarray(rec, SPEC_REC_DTYPE)
-    assert rec.size == len(nch) * MAXCH
+    c, blk, nch, chain = _chain_args(carr, blk, nch, chain)
+    rec = _rows(rec, SPEC_REC_DTYPE, len(nch) * MAXCH)
     hit = C.c_int(0)
     _check(lib().gss_carr_chain_records(_ptr(c), _ptr(blk), _ptr(nch), _ptr(chain), len(nch),
                                         int(n_per_blk), _ptr(rec), threads, C.byref(hit)))
@@ -865,9 +862,8 @@ def spec_links(nch, chain, n_per_blk, gi, spec, threads=8):
     """Each row's link from its slot's previous row (gss_spec_links): SPEC_LINK_DTYPE [nb, 16]."""
     nch = np.ascontiguousarray(nch, np.int32)
     chain = np.ascontiguousarray(chain, CHAIN_DTYPE)
-    gi = np.ascontiguousarray(gi, SPEC_IN_DTYPE)
-    spec = np.ascontiguousarray(spec, SPEC_DTYPE)
-    assert spec.size == gi.size == len(nch) * MAXCH
+    n = len(nch) * MAXCH
+    gi, spec = _rows(gi, SPEC_IN_DTYPE, n), _rows(spec, SPEC_DTYPE, n)
     link = np.zeros((len(nch), MAXCH), SPEC_LINK_DTYPE)
     _check(lib().gss_spec_links(_ptr(nch), _ptr(chain), len(nch), int(n_per_blk), _ptr(gi),
                                 _ptr(spec), _ptr(link), threads))
@@ -877,14 +873,10 @@ def spec_links(nch, chain, n_per_blk, gi, spec, threads=8):
 def carr_chain_linked(carr, blk, nch, chain, n_per_blk, gi, spec, link, threads=8):
     """carr_chain_spec's result with the rows' links (gss_carr_chain_linked): fills blk["carr0"]
     in place; returns (carrier after the last block, blocks where the translation held)."""
-    c = np.array(carr, np.float64, copy=True)
-    assert c.shape == (MAXCH,) and blk.flags.c_contiguous and blk.dtype == CHAN_DTYPE
-    nch = np.ascontiguousarray(nch, np.int32)
-    chain = np.ascontiguousarray(chain, CHAIN_DTYPE)
-    gi = np.ascontiguousarray(gi, SPEC_IN_DTYPE)
-    spec = np.ascontiguousarray(spec, SPEC_DTYPE)
-    link = np.ascontiguousarray(link, SPEC_LINK_DTYPE)
-    assert spec.size == gi.size == link.size == len(nch) * MAXCH
+    c, blk, nch, chain = _chain_args(carr, blk, nch, chain)
+    n = len(nch) * MAXCH
+    gi, spec = _rows(gi, SPEC_IN_DTYPE, n), _rows(spec, SPEC_DTYPE, n)
+    link = _rows(link, SPEC_LINK_DTYPE, n)
     hit = C.c_int(0)
     _check(lib().gss_carr_chain_linked(_ptr(c), _ptr(blk), _ptr(nch), _ptr(chain), len(nch),
                                        int(n_per_blk), _ptr(gi), _ptr(spec), _ptr(link), threads,

@@ -430,3 +430,202 @@ def test_rows_independent_of_threads_and_batches(kind):
     gb = np.frombuffer(got[0], G.CHAN_DTYPE).reshape(-1, G.MAXCH)
     fields = [f for f in G.CHAN_DTYPE.names if f != "carr0"]  # carriers: unknown after a seek
     assert all(np.array_equal(gb[f], b0[f]) for f in fields)
+
+
+# ---- the carrier-chain family (csrc/host/carr_chain.c): anchors, edges of the slot walk, errors ----
+_CHAIN_CALLS = ["exact", "spec", "anchored", "records", "linked"]
+_chain_rows_cache = {}
+
+
+def _chain_rows(kind):
+    """31 s at 1 MS/s in one batch (309 blocks, across the 30 s update): the static scenario, and
+    the circle from a start at which the update allocates a new satellite, so that a slot's chain
+    restarts in mid-batch.  With the exact chain by brute force (every row's carr0, the slots'
+    end carriers), computed once."""
+    if kind not in _chain_rows_cache:
+        kw = {"llh": LOC} if kind == "static" else \
+            {"motion_file": CIRCLE, "start": (2014, 12, 20, 17, 10, 0)}
+        s = G.Scenario(NAV, duration=31.0, samp_freq=1.0e6, **kw)
+        carr, n = s.carrier(), s.n_per_blk
+        blk, nch, chain = s.next_deferred(350, threads=8)
+        assert len(nch) == 309
+        carr0, end = _brute_chain(carr, blk, nch, chain, n)
+        _chain_rows_cache[kind] = (carr, blk, nch, chain, n, carr0, end)
+    return _chain_rows_cache[kind]
+
+
+def _brute_chain(carr, blk, nch, chain, n):
+    run = np.array(carr, np.float64)
+    carr0 = np.zeros(blk.shape)
+    for b in range(len(nch)):
+        for k in range(nch[b]):
+            sl = chain[b, k]["slot"]
+            if chain[b, k]["reset"]:
+                run[sl] = chain[b, k]["init"]
+            carr0[b, k] = run[sl]
+            run[sl] = oracle.carr_brute(run[sl], blk[b, k]["carr_step"], n)
+    return carr0, run
+
+
+def _run_chain(call, carr, blk, nch, chain, n):
+    """One of the five chains over a batch (its guesses, walks, links and records made from the
+    same batch): (end carriers, the rows' carr0)."""
+    b = blk.copy()
+    if call == "exact":
+        end, _ = G.carr_chain(carr, b, nch, chain, n, with_ck=False, threads=3)
+        return end, b["carr0"]
+    gi = G.carr_chain_guess(carr, blk, nch, chain, n)
+    spec = G.spec_host(gi, n, threads=3).reshape(gi.shape)
+    if call == "spec":
+        end, _ = G.carr_chain_spec(carr, b, nch, chain, n, gi, spec, threads=3)
+    elif call == "anchored":
+        end, _, anch = G.carr_chain_anchored(carr, b, nch, chain, n, gi, spec, threads=3)
+        assert anch.shape == gi.shape
+    elif call == "records":
+        rec = G.spec_records(gi, spec, n, threads=3)
+        end, _ = G.carr_chain_records(carr, b, nch, chain, n, rec, threads=3)
+    else:
+        link = G.spec_links(nch, chain, n, gi, spec, threads=3)
+        assert link.shape == gi.shape
+        end, _ = G.carr_chain_linked(carr, b, nch, chain, n, gi, spec, link, threads=3)
+    return end, b["carr0"]
+
+
+@pytest.mark.parametrize("kind", ["static", "circle"])
+def test_chain_anchors_match_brute_force(kind):
+    """gss_carr_chain_anchored's anchors: the same bytes as gss_carr_anchors on the rows it
+    filled; every anchor with pos >= 0 is the brute-force carrier at that sample of its row;
+    padding rows carry none (pos -1, val 0); hits and end carriers are gss_carr_chain_spec's."""
+    carr, blk, nch, chain, n, carr0, end_ref = _chain_rows(kind)
+    gi = G.carr_chain_guess(carr, blk, nch, chain, n)
+    spec = G.spec_host(gi, n, threads=8)
+    b1, b2 = blk.copy(), blk.copy()
+    end1, hit1 = G.carr_chain_spec(carr, b1, nch, chain, n, gi, spec)
+    end2, hit2, anch = G.carr_chain_anchored(carr, b2, nch, chain, n, gi, spec)
+    assert hit2 == hit1 and end2.tobytes() == end1.tobytes() == end_ref.tobytes()
+    assert b2["carr0"].tobytes() == b1["carr0"].tobytes() == carr0.tobytes()
+    assert G.carr_anchors(b2, nch, n, gi, spec, threads=3).tobytes() == anch.tobytes()
+    checked = 0
+    for b in list(range(0, len(nch), 44)) + [299, 300]:
+        for k in range(nch[b]):
+            a, row = anch[b, k], blk[b, k]
+            assert a["pos"][0] == 0 and a["val"][0] == carr0[b, k]
+            for j in np.flatnonzero(a["pos"] >= 0):
+                assert 0 <= a["pos"][j] < n
+                assert a["val"][j] == oracle.carr_brute(carr0[b, k], row["carr_step"],
+                                                        int(a["pos"][j])), (b, k, j)
+                checked += 1
+    assert checked > 500, checked
+    pad = np.arange(G.MAXCH)[None, :] >= nch[:, None]
+    assert pad.any() and (anch["pos"][pad] == -1).all() and not anch["val"][pad].any()
+
+
+@pytest.mark.parametrize("call", _CHAIN_CALLS)
+def test_chain_slot_walk_edges(call):
+    """The walk over a slot's rows that the five chains share, against brute force: a whole batch
+    with restarts on the slots' first rows and (circle) on a slot's first row in mid-batch; an
+    empty batch; a batch a slot never appears in; batches of one block."""
+    rng = np.random.default_rng(11)
+    for kind in ("static", "circle"):
+        carr, blk, nch, chain, n, carr0, end_ref = _chain_rows(kind)
+        live = np.arange(G.MAXCH)[None, :] < nch[:, None]
+        reset = (chain["reset"] != 0) & live
+        assert reset[0, :nch[0]].all()                       # restarts on the batch's first rows
+        used = set(chain["slot"][live].tolist())
+        idle = [s for s in range(G.MAXCH) if s not in used]
+        assert idle
+        # the slots' start carriers are dead where the chain restarts: any value must do
+        start = rng.random(G.MAXCH)
+        end, c0 = _run_chain(call, start, blk, nch, chain, n)
+        assert c0.tobytes() == carr0.tobytes(), kind
+        assert end[sorted(used)].tobytes() == end_ref[sorted(used)].tobytes(), kind
+        assert end[idle].tobytes() == start[idle].tobytes(), kind    # a slot that never appears
+        # no block at all: status 0, the carriers as they came
+        end, c0 = _run_chain(call, start, blk[:0], nch[:0], chain[:0], n)
+        assert end.tobytes() == start.tobytes() and c0.shape == (0, G.MAXCH)
+        # one block: the first (every row a restart) and one from the carriers before it
+        for b in (0, 305):
+            st = rng.random(G.MAXCH)
+            if b:
+                st[chain[b, :nch[b]]["slot"]] = carr0[b, :nch[b]]
+            want = st.copy()
+            for k in range(nch[b]):
+                want[chain[b, k]["slot"]] = oracle.carr_brute(carr0[b, k],
+                                                              blk[b, k]["carr_step"], n)
+            end, c0 = _run_chain(call, st, blk[b:b + 1], nch[b:b + 1], chain[b:b + 1], n)
+            assert c0.tobytes() == carr0[b:b + 1].tobytes(), (kind, b)
+            assert end.tobytes() == want.tobytes(), (kind, b)
+        if kind == "circle":
+            # the 30 s update gives slot 12 its first row, a restart, in mid-batch; before it the
+            # slot is idle, and a batch that ends there leaves its carrier alone
+            mid = np.argwhere(reset[1:])
+            assert len(mid) == 1 and mid[0][0] + 1 == 300
+            slot = int(chain[300, mid[0][1]]["slot"])
+            assert slot not in set(chain["slot"][:300][live[:300]].tolist())
+            end, c0 = _run_chain(call, start, blk[:300], nch[:300], chain[:300], n)
+            assert end[slot] == start[slot] and c0.tobytes() == carr0[:300].tobytes()
+
+
+def _chain_error_table():
+    """(function, its message, valid arguments, positions of the required pointers, of the row or
+    block count, of n_per_blk) for every public call of the chain family"""
+    nb, n = 1, 1000
+    p = G._ptr
+    carr, out = np.zeros(G.MAXCH), np.zeros(G.MAXCH)
+    blk = np.zeros((nb, G.MAXCH), G.CHAN_DTYPE)
+    nch = np.zeros(nb, np.int32)
+    chain = np.zeros((nb, G.MAXCH), G.CHAIN_DTYPE)
+    chain["slot"] = -1
+    gi = np.zeros((nb, G.MAXCH), G.SPEC_IN_DTYPE)
+    gi["k"] = 1
+    spec = np.zeros((nb, G.MAXCH), G.SPEC_DTYPE)
+    anch = np.zeros((nb, G.MAXCH), G.ANCHOR_DTYPE)
+    link = np.zeros((nb, G.MAXCH), G.SPEC_LINK_DTYPE)
+    rec = np.zeros((nb, G.MAXCH), G.SPEC_REC_DTYPE)
+    keep = (carr, out, blk, nch, chain, gi, spec, anch, link, rec)
+    rows = nb * G.MAXCH
+    head = [p(carr), p(blk), p(nch), p(chain), nb, n]
+    chain_msg = "invalid carrier-chain arguments"
+    return keep, [
+        ("gss_carr_chain", chain_msg, head + [0, None, 2], (0, 1, 2, 3), 4, 5),
+        ("gss_carr_chain_starts", "invalid carrier-guess arguments", head + [p(gi)],
+         (0, 1, 2, 3, 6), 4, 5),
+        ("gss_carr_chain_guess", "invalid carrier-guess arguments", head + [p(gi)],
+         (0, 1, 2, 3, 6), 4, 5),
+        ("gss_carr_line_end", "invalid carrier-line arguments", head + [p(out)],
+         (0, 1, 2, 3, 6), 4, 5),
+        ("gss_spec_host", "invalid speculative-walk arguments", [p(gi), rows, n, p(spec), 2],
+         (0, 3), 1, 2),
+        ("gss_carr_chain_spec", chain_msg, head + [p(gi), p(spec), 2, None],
+         (0, 1, 2, 3, 6, 7), 4, 5),
+        ("gss_carr_chain_anchored", chain_msg, head + [p(gi), p(spec), 2, None, p(anch)],
+         (0, 1, 2, 3, 6, 7), 4, 5),
+        ("gss_carr_anchors", "invalid carrier-anchor arguments",
+         [p(blk), p(nch), nb, n, p(gi), p(spec), p(anch), 2], (0, 1, 4, 5, 6), 2, 3),
+        ("gss_spec_records", "invalid spec-record arguments",
+         [p(gi), p(spec), rows, n, p(rec), 2], (0, 1, 4), 2, 3),
+        ("gss_carr_chain_records", chain_msg, head + [p(rec), 2, None], (0, 1, 2, 3, 6), 4, 5),
+        ("gss_spec_links", "invalid spec-link arguments",
+         [p(nch), p(chain), nb, n, p(gi), p(spec), p(link), 2], (0, 1, 4, 5, 6), 2, 3),
+        ("gss_carr_chain_linked", chain_msg, head + [p(gi), p(spec), p(link), 2, None],
+         (0, 1, 2, 3, 6, 7, 8), 4, 5),
+    ]
+
+
+def test_chain_argument_errors():
+    """Every public call of the chain family: the valid arguments pass; a NULL in place of any
+    required pointer, a negative count and n_per_blk = 0 each raise GSS_E_ARG (-1) with the
+    call's own message."""
+    keep, table = _chain_error_table()
+    for name, msg, args, ptrs, i_cnt, i_n in table:
+        fn = getattr(G.lib(), name)
+        assert fn(*args) == 0, name
+        bad = [(i, None) for i in ptrs] + [(i_cnt, -1), (i_n, 0)]
+        for i, v in bad:
+            a = list(args)
+            a[i] = v
+            with pytest.raises(G.GssError) as e:
+                G._check(fn(*a))
+            assert e.value.code == -1, (name, i)
+            assert str(e.value) == f"gpssim_amd error -1: {msg}", (name, i)
+    del keep
