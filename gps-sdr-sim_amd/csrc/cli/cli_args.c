@@ -53,16 +53,63 @@ static int parse_real(const char *s, double *v)
     return *end != '\0' || !isfinite(*v);
 }
 
+/* One --jam value into c->jam[c->n_jam]:
+     cw,<js_db>,<f_hz>[,pulse,<period_s>,<duty>]
+     sweep,<js_db>,<f0_hz>,<f1_hz>,<sweep_s>[,pulse,<period_s>,<duty>]
+   at the rate the run uses (a multiple of 10 Hz, gpssim.c:1877-1881), by gss_jam_make. */
+static int jam_option(gss_cli_t *c, const char *val)
+{
+    char buf[256], *f[9];
+    int nf = 0;
+    if (strlen(val) >= sizeof buf)
+        goto bad;
+    strcpy(buf, val);
+    for (char *p = buf;; p++) {
+        if (nf == 9)
+            goto bad;
+        f[nf++] = p;
+        p = strchr(p, ',');
+        if (!p)
+            break;
+        *p = '\0';
+    }
+    const int sweep = strcmp(f[0], "sweep") == 0;
+    const int base = sweep ? 5 : 3;
+    if ((!sweep && strcmp(f[0], "cw") != 0) || (nf != base && nf != base + 3) ||
+        (nf == base + 3 && strcmp(f[base], "pulse") != 0))
+        goto bad;
+    double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   /* js f0 f1 sweep_s period_s duty */
+    if (parse_real(f[1], &v[0]) || parse_real(f[2], &v[1]))
+        goto bad;
+    if (sweep && (parse_real(f[3], &v[2]) || parse_real(f[4], &v[3]) || !(v[3] > 0.0)))
+        goto bad;
+    if (nf == base + 3 &&
+        (parse_real(f[base + 1], &v[4]) || parse_real(f[base + 2], &v[5]) || !(v[4] > 0.0)))
+        goto bad;
+    const double fs = floor(c->opt.samp_freq / 10.0) * 10.0;
+    if (gss_jam_make(fs, v[0], v[1], v[2], v[3], v[4], v[5], &c->jam[c->n_jam]))
+        goto bad;
+    c->n_jam++;
+    return 0;
+bad:
+    fprintf(stderr, "ERROR: Invalid jammer (cw,<js_db>,<f_hz> or sweep,<js_db>,<f0_hz>,<f1_hz>,"
+                    "<sweep_s>, then optionally ,pulse,<period_s>,<duty>).\n");
+    return 1;
+}
+
 /* The noise options into c->impair.
      --cn0=<dB-Hz>        sigma = 250 sqrt(fs / (2 10^(cn0/10))) LSB per component: 250 is the carrier
                           table's amplitude, so this is the C/N0 of a satellite at gain 128 (path
                           loss 1 at antenna boresight); fs as the run uses it, a multiple of 10 Hz
                           (gpssim.c:1877-1881)
      --noise-sigma=<LSB>  sigma directly
-     --noise-shift=<s>    0..8, or auto (default): the least s with (4 sigma + 2047) / 2^s <= R, R =
-                          32767 for -b 16 and 2047 for -b 8 (what >> 4 takes to the 8-bit range);
-                          0 for -b 1, which keeps only the sign
-     --seed=<u64>         default 0 */
+     --noise-shift=<s>    0..8, or auto (default): the least s with (4 sigma + 2047 + J) / 2^s <=
+                          R, R = 32767 for -b 16 and 2047 for -b 8 (what >> 4 takes to the 8-bit
+                          range), J = sum of the jammers' amp 250 / 65536 (0 without --jam); 0 for
+                          -b 1, which keeps only the sign
+     --seed=<u64>         default 0
+   With --jam and neither --cn0 nor --noise-sigma: sigma 0 (--noise-shift is then accepted,
+   --seed is not). */
 static int noise_options(gss_cli_t *c, const char *o_cn0, const char *o_sigma, const char *o_shift,
                          const char *o_seed)
 {
@@ -71,14 +118,17 @@ static int noise_options(gss_cli_t *c, const char *o_cn0, const char *o_sigma, c
         return 1;
     }
     if (!o_cn0 && !o_sigma) {
-        if (o_shift || o_seed) {
+        if (o_seed || (o_shift && c->n_jam == 0)) {
             fprintf(stderr, "ERROR: --noise-shift and --seed need --cn0 or --noise-sigma.\n");
             return 1;
         }
-        return 0;
+        if (c->n_jam == 0)
+            return 0;
     }
-    double v = 0.0, q8;
-    if (o_cn0) {
+    double v = 0.0, q8 = 0.0;
+    if (!o_cn0 && !o_sigma) {
+        /* jammers alone: no noise */
+    } else if (o_cn0) {
         if (parse_real(o_cn0, &v) || v < -100.0 || v > 200.0) {
             fprintf(stderr, "ERROR: Invalid C/N0.\n");
             return 1;
@@ -104,7 +154,9 @@ static int noise_options(gss_cli_t *c, const char *o_cn0, const char *o_sigma, c
         }
         c->impair.shift = (int32_t)v;
     } else {
-        const double peak = 4.0 * (q8 / 256.0) + 2047.0;
+        double peak = 4.0 * (q8 / 256.0) + 2047.0;
+        for (int i = 0; i < c->n_jam; i++)
+            peak += (double)c->jam[i].amp * 250.0 / 65536.0;
         const double room = c->opt.data_format == GSS_FMT_SC16 ? 32767.0 : 2047.0;
         int s = 0;
         while (c->opt.data_format != GSS_FMT_SC01 && s < 8 && peak > room * (double)(1 << s))
@@ -146,7 +198,18 @@ int gss_cli_parse(int argc, char **argv, gss_cli_t *c)
     /* additive noise (extensions, taken out the same way): --cn0=<dB-Hz> or --noise-sigma=<LSB>,
        --noise-shift=<0..8|auto>, --seed=<u64>; resolved once -s and -b are known */
     const char *o_cn0 = NULL, *o_sigma = NULL, *o_shift = NULL, *o_seed = NULL;
+    /* jammers (--jam=..., repeatable): resolved with them, in the order given */
+    const char *o_jam[GSS_MAXJAM];
+    int n_ojam = 0;
     for (int i = 0; i < argc; i++) {
+        if (i > 0 && strncmp(argv[i], "--jam=", 6) == 0) {
+            if (n_ojam == GSS_MAXJAM) {
+                fprintf(stderr, "ERROR: At most %d jammers.\n", GSS_MAXJAM);
+                return 1;
+            }
+            o_jam[n_ojam++] = argv[i] + 6;
+            continue;
+        }
         if (i > 0 && strncmp(argv[i], "--cn0=", 6) == 0) {
             o_cn0 = argv[i] + 6;
             continue;
@@ -276,5 +339,8 @@ int gss_cli_parse(int argc, char **argv, gss_cli_t *c)
         fprintf(stderr, "ERROR: Invalid duration.\n");
         return 1;
     }
+    for (int i = 0; i < n_ojam; i++)
+        if (jam_option(c, o_jam[i]))
+            return 1;
     return noise_options(c, o_cn0, o_sigma, o_shift, o_seed);
 }

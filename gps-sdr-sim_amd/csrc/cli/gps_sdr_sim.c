@@ -331,7 +331,7 @@ static int run_rank(const gss_cli_t *cli, gss_scn *scn, const gss_scn_info_t *in
     /* the noise does not change the carriers, so the hand-off stays as it is */
     gss_run_opts_t ro = {handoff ? handoff_in : NULL, handoff ? handoff_out : NULL, &h,
                          handoff && spec ? handoff_predict : NULL,
-                         cli->has_impair ? &cli->impair : NULL};
+                         cli->has_impair ? &cli->impair : NULL, cli->jam, cli->n_jam};
     if (run_id && *run_id) {
         if (rank > 0)
             snprintf(h.in_path, sizeof h.in_path, "%s.gss-carr-%s-%lld", cli->out_file, run_id,
@@ -384,6 +384,10 @@ int main(int argc, char **argv)
     if (cli.has_impair && rank == 0)
         fprintf(stderr, "Noise: sigma_q8 = %u, shift = %d, seed = %llu\n", cli.impair.sigma_q8,
                 cli.impair.shift, (unsigned long long)cli.impair.seed);
+    for (int i = 0; i < cli.n_jam && rank == 0; i++)
+        fprintf(stderr, "Jammer %d: step0 = %llu, rate = %llu, sweep = %u, amp = %u, gate = %u / %u\n",
+                i, (unsigned long long)cli.jam[i].step0, (unsigned long long)cli.jam[i].rate,
+                cli.jam[i].sweep, cli.jam[i].amp, cli.jam[i].gate_on, cli.jam[i].gate_period);
     if (world > 1)
         return run_rank(&cli, scn, &info, rank, world);
 
@@ -410,6 +414,8 @@ int main(int argc, char **argv)
     gss_run_opts_t ro;
     memset(&ro, 0, sizeof ro);
     ro.impair = &cli.impair;
+    ro.jam = cli.jam;
+    ro.n_jam = cli.n_jam;
     if (gss_run_ex(dev, scn, 0, -1, batch, threads, write_sink, fp,
                    cli.has_impair ? &ro : NULL)) {
         fprintf(stderr, "\nERROR: %s\n", gss_last_error());

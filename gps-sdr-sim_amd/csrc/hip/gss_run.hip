@@ -75,6 +75,7 @@
 
 extern "C" int gss_fail(int code, const char *fmt, ...);
 extern "C" void gss_pool_select(int id);             /* pool.c */
+extern "C" int gss_jam_check(const gss_jam_t *jam, int n_jam);   /* jam.c */
 /* n bytes from src to dst by a copy kernel on st: pinned host or device memory on either side
    (gss_producers.hip; not exported) */
 int run_copy_launch(void *dst, const void *src, size_t n, hipStream_t st);
@@ -85,6 +86,11 @@ extern "C" __attribute__((weak)) int gss_impair_device(gss_dev *d, const gss_imp
                                                        const int16_t *iq, uint64_t sample0,
                                                        size_t n, int fmt, void *out,
                                                        void *stream);
+/* ... and the jammers' (gss_jam.hip), which takes its place in a run with jammers */
+extern "C" __attribute__((weak)) int gss_jam_device(gss_dev *d, const gss_impair_t *p,
+                                                    const gss_jam_t *jam, int n_jam,
+                                                    const int16_t *iq, uint64_t sample0, size_t n,
+                                                    int fmt, void *out, void *stream);
 
 #define RUN_TRY(x)                                                                           \
     do {                                                                                     \
@@ -404,6 +410,8 @@ struct Run {
     const gss_run_opts_t *opts;      /* carrier hand-off (gss_run_ex), or null */
     const gss_impair_t *impair = nullptr;   /* additive noise (opts->impair), or null: the blocks
                                                render at SC16 and the impairment writes fmt_out */
+    gss_jam_t jam[GSS_MAXJAM];              /* the run's copy of opts->jam */
+    int n_jam = 0;
     int fmt_out = 0;                 /* the scenario's format: what the sink receives          */
     /* with opts->carr_in: the whole range planned up front (rows, carriers, checkpoints) */
     std::vector<gss_chan_blk_t> pre_blk;
@@ -1373,8 +1381,11 @@ int impair_blocks(Run &r, Slot &sl, int b0, int nblk, hipStream_t st)
     const size_t n = (size_t)r.n_per_blk;
     uint8_t *in = sl.d_out + 4 * n * (size_t)b0;
     uint8_t *out = sl.d_imp ? sl.d_imp + gss_block_bytes(r.n_per_blk, r.fmt_out) * (size_t)b0 : in;
-    return gss_impair_device(r.dev, r.impair, (const int16_t *)in,
-                             (uint64_t)(sl.first + b0) * (uint64_t)n, n * (size_t)nblk, r.fmt_out,
+    const uint64_t s0 = (uint64_t)(sl.first + b0) * (uint64_t)n;
+    if (r.n_jam > 0)
+        return gss_jam_device(r.dev, r.impair, r.jam, r.n_jam, (const int16_t *)in, s0,
+                              n * (size_t)nblk, r.fmt_out, out, st);
+    return gss_impair_device(r.dev, r.impair, (const int16_t *)in, s0, n * (size_t)nblk, r.fmt_out,
                              out, st);
 }
 
@@ -1983,6 +1994,15 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
     if (imp && !gss_impair_device)
         return gss_fail(GSS_E_STATE, "additive noise requested, but this build has no "
                                      "impairment launch (gss_impair_device)");
+    const int n_jam = opts ? opts->n_jam : 0;
+    if (n_jam < 0 || n_jam > GSS_MAXJAM || (n_jam > 0 && (!imp || !opts->jam)))
+        return gss_fail(GSS_E_ARG, "invalid jammers (0..%d of them, with an impairment for "
+                                   "the shift)", GSS_MAXJAM);
+    if (n_jam > 0 && (rc = gss_jam_check(opts->jam, n_jam)) != 0)
+        return rc;
+    if (n_jam > 0 && !gss_jam_device)
+        return gss_fail(GSS_E_STATE, "jammers requested, but this build has no jammer launch "
+                                     "(gss_jam_device)");
     const size_t bb_r = imp ? (size_t)info.n_per_blk * 4 : bb;
     if (batch <= 0)
         batch = 100;
@@ -2001,6 +2021,9 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
     r.dev = d;
     r.opts = opts;
     r.impair = imp;
+    r.n_jam = n_jam;
+    for (int i = 0; i < n_jam; i++)
+        r.jam[i] = opts->jam[i];
     r.fmt = imp ? GSS_FMT_SC16 : info.data_format;
     r.fmt_out = info.data_format;
     r.bb = bb;

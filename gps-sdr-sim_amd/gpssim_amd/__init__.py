@@ -128,6 +128,28 @@ class Impair(C.Structure):
         return f"Impair(sigma_q8={self.sigma_q8}, shift={self.shift}, seed={self.seed})"
 
 
+MAXJAM = 4                                         # GSS_MAXJAM
+
+
+class Jam(C.Structure):
+    """gss_jam_t: one jammer in the definition's integers (include/gpssim_amd.h); jam_make() fills
+    one from physical parameters."""
+    _fields_ = [("step0", C.c_uint64), ("rate", C.c_uint64), ("phase0", C.c_uint64),
+                ("sweep", C.c_uint32), ("amp", C.c_uint32), ("gate_period", C.c_uint32),
+                ("gate_on", C.c_uint32), ("gate_shift", C.c_uint32), ("pad", C.c_uint32)]
+
+    def __init__(self, step0=0, rate=0, phase0=0, sweep=1, amp=0, gate_period=0, gate_on=0,
+                 gate_shift=0, pad=0):
+        m = 2**64 - 1
+        super().__init__(int(step0) & m, int(rate) & m, int(phase0) & m, int(sweep), int(amp),
+                         int(gate_period), int(gate_on), int(gate_shift), int(pad))
+
+    def __repr__(self):
+        return (f"Jam(step0={self.step0}, rate={self.rate}, phase0={self.phase0}, "
+                f"sweep={self.sweep}, amp={self.amp}, gate_period={self.gate_period}, "
+                f"gate_on={self.gate_on}, gate_shift={self.gate_shift}, pad={self.pad})")
+
+
 class Acq(C.Structure):
     """gss_acq_t: an acquisition search.  fs_hz, fmt (16 / 8 / 1), coh_ms x n_coh windows, bins
     -n_half..n_half of bin_hz (default 500 / coh_ms), qshift (-1: auto), prns (iterable of 1..32,
@@ -190,12 +212,14 @@ class _Truth(C.Structure):                           # gss_acq_truth_t
 
 class _Cli(C.Structure):
     _fields_ = [("opt", _Opts), ("nav_file", C.c_char * 256), ("motion_file", C.c_char * 256),
-                ("out_file", C.c_char * 256), ("impair", Impair), ("has_impair", C.c_int)]
+                ("out_file", C.c_char * 256), ("impair", Impair), ("has_impair", C.c_int),
+                ("jam", Jam * MAXJAM), ("n_jam", C.c_int)]
 
 
 class _RunOpts(C.Structure):                         # gss_run_opts_t
     _fields_ = [("carr_in", C.c_void_p), ("carr_out", C.c_void_p), ("carr_user", C.c_void_p),
-                ("carr_predict", C.c_void_p), ("impair", C.POINTER(Impair))]
+                ("carr_predict", C.c_void_p), ("impair", C.POINTER(Impair)),
+                ("jam", C.POINTER(Jam)), ("n_jam", C.c_int)]
 
 
 class _Info(C.Structure):
@@ -241,6 +265,11 @@ _SIGS = {
     "gss_impair_host": (C.c_int, [C.POINTER(Impair), _P, C.c_uint64, C.c_size_t, C.c_int, _P]),
     "gss_impair_device": (C.c_int, [_P, C.POINTER(Impair), _P, C.c_uint64, C.c_size_t, C.c_int,
                                     _P, _P]),
+    "gss_jam_make": (C.c_int, [C.c_double] * 7 + [C.POINTER(Jam)]),
+    "gss_jam_host": (C.c_int, [C.POINTER(Impair), C.POINTER(Jam), C.c_int, _P, C.c_uint64,
+                               C.c_size_t, C.c_int, _P]),
+    "gss_jam_device": (C.c_int, [_P, C.POINTER(Impair), C.POINTER(Jam), C.c_int, _P, C.c_uint64,
+                                 C.c_size_t, C.c_int, _P, _P]),
     "gss_acq_sizes": (C.c_int, [C.POINTER(Acq), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32)]),
@@ -398,6 +427,34 @@ def impair_host(imp, iq, sample0, fmt):
     n = len(iq) // 2
     out = np.zeros(impair_bytes(n, fmt) if fmt in (1, 8, 16) else 0, np.uint8)
     _check(lib().gss_impair_host(C.byref(imp), _ptr(iq), int(sample0), n, int(fmt), _ptr(out)))
+    return out
+
+
+def _jam_array(jam):
+    """(ctypes array or None, count) of an iterable of Jam; the count is passed on as it is, so
+    that the library refuses more than MAXJAM"""
+    jam = list(jam or ())
+    return ((Jam * len(jam))(*jam) if jam else None), len(jam)
+
+
+def jam_make(fs_hz, js_db, f0_hz, f1_hz=0.0, sweep_s=0.0, gate_period_s=0.0, duty=0.0):
+    """A Jam from physical parameters (gss_jam_make): J/S in dB against a satellite at gain 128,
+    a tone at f0_hz (sweep_s 0) or a sweep f0_hz -> f1_hz every sweep_s seconds, optionally pulsed
+    with gate_period_s and duty."""
+    j = Jam()
+    _check(lib().gss_jam_make(float(fs_hz), float(js_db), float(f0_hz), float(f1_hz),
+                              float(sweep_s), float(gate_period_s), float(duty), C.byref(j)))
+    return j
+
+
+def jam_host(imp, jam, iq, sample0, fmt):
+    """gss_jam_host: impair_host with the jammers `jam` (an iterable of Jam) added."""
+    iq = np.ascontiguousarray(iq, np.int16).reshape(-1)
+    n = len(iq) // 2
+    out = np.zeros(impair_bytes(n, fmt) if fmt in (1, 8, 16) else 0, np.uint8)
+    arr, nj = _jam_array(jam)
+    _check(lib().gss_jam_host(C.byref(imp), arr, nj, _ptr(iq), int(sample0), n, int(fmt),
+                              _ptr(out)))
     return out
 
 
@@ -624,9 +681,12 @@ class Scenario:
         self._init_info()
         if cli.has_impair:                             # --cn0 / --noise-sigma (Device.run(impair=))
             self.impair = Impair(cli.impair.sigma_q8, cli.impair.shift, cli.impair.seed)
+        if cli.n_jam:                                  # --jam (Device.run(jam=))
+            self.jam = [Jam.from_buffer_copy(cli.jam[i]) for i in range(cli.n_jam)]
         return self, cli.out_file.decode()
 
     impair = None                # the command line's noise options (from_cli), else None
+    jam = None                   # the command line's jammers (from_cli: a list of Jam), else None
 
     def _init_info(self):
         inf = _Info()
@@ -963,6 +1023,13 @@ class Device:
                                        int(n), int(fmt), C.c_void_p(out_ptr),
                                        C.c_void_p(stream or None)))
 
+    def jam_device(self, imp, jam, iq_ptr, sample0, n, fmt, out_ptr, stream=0):
+        """gss_jam_device: impair_device with the jammers `jam` (an iterable of Jam) added."""
+        arr, nj = _jam_array(jam)
+        _check(lib().gss_jam_device(self._h, C.byref(imp), arr, nj, C.c_void_p(iq_ptr),
+                                    int(sample0), int(n), int(fmt), C.c_void_p(out_ptr),
+                                    C.c_void_p(stream or None)))
+
     def acquire(self, acq, samples_ptr, peaks_ptr, grid_ptr=0, qshift_ptr=0, stream=0):
         """gss_acquire_device: the acquisition search over the samples at device pointer
         samples_ptr; peaks (n_prn x 32 bytes), the optional grid and resolved shift go to device
@@ -1001,11 +1068,14 @@ class Device:
                                _ptr(rec), pitch, _ptr(count)))
         return rec, count
 
-    def run(self, scn, sink, first_block=0, n_blocks=-1, batch=100, threads=8, impair=None):
+    def run(self, scn, sink, first_block=0, n_blocks=-1, batch=100, threads=8, impair=None,
+            jam=None):
         """Stream blocks [first_block, first_block + n_blocks) of Scenario scn through gss_run;
         sink(memoryview, first_block, nblocks) gets each batch's bytes in run order (the view
         is valid only during the call).  An exception in sink stops the run and is re-raised.
-        impair: an Impair (additive noise, gss_run_opts_t.impair), None: off."""
+        impair: an Impair (additive noise, gss_run_opts_t.impair), None: off.  jam: an iterable of
+        Jam (gss_run_opts_t.jam), None: none; jammers need an impair (its shift; sigma_q8 0: no
+        noise)."""
         err = []
 
         def _sink(user, ptr, n, first, nb):
@@ -1017,10 +1087,12 @@ class Device:
                 return 1
 
         cb = SINK_FN(_sink)
-        if impair is None:
+        arr, nj = _jam_array(jam)
+        if impair is None and nj == 0:
             rc = lib().gss_run(self._h, scn._h, first_block, n_blocks, batch, threads, cb, None)
         else:
-            ro = _RunOpts(None, None, None, None, C.pointer(impair))
+            ro = _RunOpts(None, None, None, None, C.pointer(impair) if impair is not None else None,
+                          arr, nj)
             rc = lib().gss_run_ex(self._h, scn._h, first_block, n_blocks, batch, threads, cb,
                                   None, C.byref(ro))
         if err:

@@ -234,6 +234,61 @@ int gss_impair_host(const gss_impair_t *p, const int16_t *iq, uint64_t sample0, 
 int gss_impair_device(gss_dev *d, const gss_impair_t *p, const int16_t *iq, uint64_t sample0,
                       size_t n, int fmt, void *out, void *stream);
 
+/* ---- jammers ----------------------------------------------------------------------------------
+   Up to GSS_MAXJAM interferers added to the 16-bit samples beside the noise, before the format's
+   quantiser (an extension): a tone, a linear sweep that repeats every P samples, either gated
+   by a pulse.  Exact integer arithmetic mod 2^64, a function of the sample's absolute index n
+   alone (the n of the noise), so the bytes do not depend on batches, windows or ranks:
+     k = n div P,  m = n mod P
+     PhiP = P step0 + rate (P (P - 1) / 2)                (the half taken before the product)
+     Phi  = phase0 + k PhiP + m step0 + rate (m (m - 1) / 2)
+     idx  = Phi >> 55                                      (0..511)
+     on   = gate_period == 0 || ((n mod gate_period) + gate_shift) mod gate_period < gate_on
+     jI = on ? (amp cos512[idx] + 2^15) >> 16 : 0          (arithmetic; tables of gss_lut)
+     jQ = on ? (amp sin512[idx] + 2^15) >> 16 : 0
+     output  w = (x16 + sum_j jI_j + g + ((1 << shift) >> 1)) >> shift  (Q alike with jQ)
+   with g, the clamps and the packing of gss_impair_t above (sigma_q8 = 0: g is 0, a jammer
+   without noise).  The phase is continuous across sweeps; rate = 0, P = 1 is a tone, Phi =
+   phase0 + n step0.  Level: amp = 65536 writes the carrier table's 250, the amplitude of a
+   satellite at gain 128 (the convention of --cn0): J/S = 0 dB against it, as power while the
+   gate is on; amp <= 2^23 (42.1 dB) keeps amp 250 + 2^15 inside int32.                        */
+#define GSS_MAXJAM 4
+typedef struct gss_jam {
+    uint64_t step0;        /* carrier step at the start of a sweep, 2^-64 cycle per sample (two's
+                              complement)                                                      */
+    uint64_t rate;         /* added to the step every sample, 2^-64 cycle per sample^2 (two's
+                              complement); CW: 0                                               */
+    uint64_t phase0;       /* phase of sample 0, 2^-64 cycle                                   */
+    uint32_t sweep;        /* P >= 1: samples per sweep (CW: 1)                                */
+    uint32_t amp;          /* 0..2^23: peak amplitude in 1/65536 of the carrier table's 250    */
+    uint32_t gate_period;  /* 0: always on; else samples per pulse period                      */
+    uint32_t gate_on;      /* 0..gate_period samples on                                        */
+    uint32_t gate_shift;   /* 0..gate_period-1 (0 when gate_period is 0)                       */
+    uint32_t pad;          /* 0                                                                */
+} gss_jam_t;               /* 48 bytes */
+
+/* A jammer from physical parameters, in IEEE double exactly as written here:
+     step(f) = (int64) floor(f / fs_hz * 2^64 + 0.5)                     requires |f| < fs_hz / 2
+     sweep_s == 0 (CW):  P = 1, rate = 0, step0 = step(f0_hz)            (f1_hz is not read)
+     sweep_s > 0:        P = floor(sweep_s * fs_hz + 0.5) in 1..2^32-1, step0 = step(f0_hz),
+                         rate = floor((step(f1_hz) - step(f0_hz)) / P)   (integers, floored)
+     amp = floor(65536 * pow(10, js_db / 20) + 0.5) <= 2^23
+     gate_period = floor(gate_period_s * fs_hz + 0.5) <= 2^32-1 (gate_period_s == 0: no gate),
+     gate_on = floor(duty * gate_period + 0.5) with 0 <= duty <= 1, gate_shift = 0, phase0 = 0
+   GSS_E_ARG for anything out of range (a gate_period_s > 0 that rounds to 0 included).        */
+int gss_jam_make(double fs_hz, double js_db, double f0_hz, double f1_hz, double sweep_s,
+                 double gate_period_s, double duty, gss_jam_t *out);
+/* gss_impair_host with n_jam (0..GSS_MAXJAM) jammers added; p is required (its shift applies;
+   sigma_q8 = 0: no noise); the buffer rules are gss_impair_host's; n_jam = 0: its bytes.
+   GSS_E_ARG for a jammer with sweep = 0, amp > 2^23, gate_on > gate_period, gate_shift >=
+   max(gate_period, 1) or pad != 0.                                                            */
+int gss_jam_host(const gss_impair_t *p, const gss_jam_t *jam, int n_jam, const int16_t *iq,
+                 uint64_t sample0, size_t n, int fmt, void *out);
+/* The same on the device: device pointers, asynchronous on stream; jam is a host array, read
+   before the call returns.                                                                    */
+int gss_jam_device(gss_dev *d, const gss_impair_t *p, const gss_jam_t *jam, int n_jam,
+                   const int16_t *iq, uint64_t sample0, size_t n, int fmt, void *out, void *stream);
+
 /* ---- signal acquisition -------------------------------------------------------------------------
    A measurement of generated samples (an extension; the reference has no receiver): for every
    selected PRN a search over Doppler bins and code phases, the peak, and the noise floor around
@@ -451,6 +506,11 @@ typedef struct gss_cli {
     /* extensions: --cn0=<dB-Hz> | --noise-sigma=<LSB>, --noise-shift=<0..8|auto>, --seed=<u64> */
     gss_impair_t impair;
     int has_impair;
+    /* --jam=cw,<js_db>,<f_hz>[,pulse,<period_s>,<duty>] |
+       --jam=sweep,<js_db>,<f0_hz>,<f1_hz>,<sweep_s>[,pulse,<period_s>,<duty>], up to GSS_MAXJAM
+       times (gss_jam_make at the run's rate); sets has_impair (sigma_q8 = 0 without noise)    */
+    gss_jam_t jam[GSS_MAXJAM];
+    int n_jam;
 } gss_cli_t;
 int gss_cli_parse(int argc, char **argv, gss_cli_t *cli);
 void gss_cli_usage(void);
@@ -718,7 +778,8 @@ int gss_run(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int b
    first_block (it may block until the process before has them), walks the carrier chain over
    the range (gss_carr_chain) and hands the end state to carr_out (if set) -- before the first
    batch renders.  Both callbacks return 0, or non-zero to abort the run (GSS_E_IO).
-   opts == NULL or carr_in == NULL: gss_run (blocks before first_block planned and dropped).  */
+   opts == NULL: gss_run.  carr_in == NULL: blocks before first_block are planned and dropped
+   as in gss_run; impair and jam apply either way.                                            */
 typedef struct gss_run_opts {
     int (*carr_in)(void *user, double *carr);             /* [GSS_MAXCH], out                  */
     int (*carr_out)(void *user, const double *carr);      /* [GSS_MAXCH]                       */
@@ -738,6 +799,10 @@ typedef struct gss_run_opts {
     /* Optional (NULL: off): additive noise.  Every block renders at SC16 and the impairment
        (gss_impair_device, sample0 = run block * n_per_blk) writes the scenario's format.       */
     const gss_impair_t *impair;
+    /* Optional (n_jam 0: none): jammers, copied when the run starts.  They need impair (its
+       shift; sigma_q8 = 0 for no noise); gss_jam_device then takes gss_impair_device's place. */
+    const gss_jam_t *jam;
+    int n_jam;
 } gss_run_opts_t;
 int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int batch,
                int threads, gss_sink_fn sink, void *user, const gss_run_opts_t *opts);
