@@ -135,6 +135,19 @@ int    rinex_read(eph_t eph[][K_MAX_SAT], iono_t *io, const char *fname);
 int    motion_read_csv(double (*xyz)[3], int cap, const char *fname);
 int    motion_read_nmea(double (*xyz)[3], int cap, const char *fname);
 
+/* ---- navdata.c ---------------------------------------------------------------------------- */
+struct gss_navdata {                 /* include/gpssim_amd.h, gss_navdata_* */
+    int n_sets;                      /* RINEX sets held (0: a handle opened empty)               */
+    eph_t sets[K_EPH_SETS][K_MAX_SAT];
+    iono_t io;
+    eph_t cur[K_MAX_SAT];            /* the ephemeris in use per PRN (vflg)                      */
+    uint32_t sf[K_MAX_SAT][3][K_N_DWRD_SBF];   /* the 24 data bits of subframes 1-3 as decoded   */
+    int have[K_MAX_SAT][3];
+    int wn[K_MAX_SAT];               /* week number mod 1024 of subframe 1                       */
+};
+/* the ephemeris a fix at second-of-week sec uses for prn, or NULL */
+const eph_t *navdata_eph(const gss_navdata *h, int prn, double sec);
+
 /* ---- pool.c ------------------------------------------------------------------------------- */
 typedef void (*gss_task_fn)(void *arg, int part);
 int    gss_pool_run(int nthreads, int nparts, gss_task_fn fn, void *arg);

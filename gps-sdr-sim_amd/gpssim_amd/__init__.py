@@ -25,6 +25,7 @@ IN_TREE = os.path.abspath(LIB_PATH) == os.path.abspath(_INTREE)
 CLI_PATH = os.path.join(PKG_DIR, "bin", "gps-sdr-sim")
 ACQ_CLI_PATH = os.path.join(PKG_DIR, "bin", "gps-sdr-acq")
 TRK_CLI_PATH = os.path.join(PKG_DIR, "bin", "gps-sdr-track")
+PVT_CLI_PATH = os.path.join(PKG_DIR, "bin", "gps-sdr-pvt")
 
 MAXCH = 16
 CA_WORDS = 32
@@ -96,6 +97,19 @@ assert TRK_JOB_DTYPE.itemsize == 24
 NAV_SF_DTYPE = np.dtype([("sample", "<i8"), ("epoch", "<i4"), ("polarity", "<i4"),
                          ("tow", "<i4"), ("id", "<i4"), ("word", "<u4", (10,))])
 assert NAV_SF_DTYPE.itemsize == 64
+# gss_obs_t: code phase and accumulated carrier of one job at one instant (gss_obs_*)
+OBS_DTYPE = np.dtype([("code", "<i8"), ("adr", "<i8"), ("epoch", "<i4"), ("w", "<i4"),
+                      ("pad", "<i8")])
+assert OBS_DTYPE.itemsize == 32
+# gss_pvt_sat_t: one satellite of a fix (gss_pvt_solve)
+PVT_SAT_DTYPE = np.dtype([("obs", OBS_DTYPE), ("prn", "<i4"), ("sf_epoch", "<i4"),
+                          ("sf_tow", "<i4"), ("pad", "<i4")])
+assert PVT_SAT_DTYPE.itemsize == 48
+NAVDATA_FIELDS = ("valid", "iode", "iodc", "toc", "toe", "af0", "af1", "af2", "tgd", "crs",
+                  "deltan", "m0", "cuc", "ecc", "cus", "sqrta", "cic", "omg0", "cis", "inc0",
+                  "crc", "aop", "omgdot", "idot", "iono_valid", "alpha0", "alpha1", "alpha2",
+                  "alpha3", "beta0", "beta1", "beta2", "beta3", "week")   # GSS_NAVDATA_FIELDS
+PVT_OK, PVT_FEW, PVT_SINGULAR, PVT_DIVERGED = 0, 1, 2, 3
 
 
 class GssError(RuntimeError):
@@ -205,6 +219,20 @@ class Trk(C.Structure):
                 f"Ki={self.Ki}, Kp={self.Kp}, Kd={self.Kd})")
 
 
+class _PvtOpts(C.Structure):                         # gss_pvt_opts_t
+    _fields_ = [("no_iono", C.c_int32), ("week", C.c_int32)]
+
+
+class PvtFix(C.Structure):
+    """gss_pvt_fix_t: what gss_pvt_solve returns (status PVT_OK, PVT_FEW, PVT_SINGULAR or
+    PVT_DIVERGED; T0 = t0_floor + t0_frac seconds of week t0_week)"""
+    _fields_ = [("xyz", C.c_double * 3), ("llh", C.c_double * 3), ("vel", C.c_double * 3),
+                ("t0_sec", C.c_double), ("t0_frac", C.c_double), ("t0_floor", C.c_double),
+                ("drift", C.c_double), ("pdop", C.c_double), ("rms", C.c_double),
+                ("t0_week", C.c_int32), ("n_used", C.c_int32), ("status", C.c_int32),
+                ("iterations", C.c_int32)]
+
+
 class _Truth(C.Structure):                           # gss_acq_truth_t
     _fields_ = [("tau", C.c_double), ("doppler_hz", C.c_double), ("cn0_offset_db", C.c_double),
                 ("prn", C.c_int32), ("pad", C.c_int32)]
@@ -287,6 +315,20 @@ _SIGS = {
     "gss_track": (C.c_int, [_P, C.POINTER(Trk), _P, C.c_int64, _P, C.c_int, _P, C.c_int64, _P]),
     "gss_nav_decode": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int, C.POINTER(C.c_int32)]),
     "gss_trk_cn0": (C.c_double, [_P, C.c_int64, C.c_int64]),
+    "gss_obs_host": (C.c_int, [C.c_int32, _P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64,
+                               C.c_int32, _P, C.c_int]),
+    "gss_obs_device": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64,
+                                 C.c_int32, _P, _P]),
+    "gss_obs": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64,
+                          C.c_int32, _P]),
+    "gss_navdata_open_rinex": (C.c_int, [C.POINTER(_P), C.c_char_p]),
+    "gss_navdata_open_empty": (C.c_int, [C.POINTER(_P)]),
+    "gss_navdata_add_subframe": (C.c_int, [_P, C.c_int, _P]),
+    "gss_navdata_get": (C.c_int, [_P, C.c_int, _P, C.c_int]),
+    "gss_navdata_close": (C.c_int, [_P]),
+    "gss_pvt_solve": (C.c_int, [_P, C.c_double, C.c_int64, _P, C.c_int, C.POINTER(_PvtOpts),
+                                C.POINTER(PvtFix)]),
+    "gss_pvt_range": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P]),
     "gss_dev_timing": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float),
                                  C.POINTER(C.c_float)]),
     "gss_dev_timing_lin": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
@@ -555,6 +597,80 @@ def trk_cn0(rec, skip=500):
     """tracked C/N0 [dB-Hz] of one job's records from epoch skip on (gss_trk_cn0)"""
     rec = np.ascontiguousarray(rec, TRK_REC_DTYPE).reshape(-1)
     return float(lib().gss_trk_cn0(_ptr(rec), len(rec), int(skip)))
+
+
+def _obs_args(rec, count):
+    rec = np.ascontiguousarray(rec, TRK_REC_DTYPE)
+    if rec.ndim != 2:
+        raise ValueError("rec must be [n_job, pitch]")
+    count = np.ascontiguousarray(count, np.int32).reshape(-1)
+    if len(count) != rec.shape[0]:
+        raise ValueError("one count per job")
+    return rec, count
+
+
+def observables_host(fs_hz, rec, count, t_first, step, n_fix, threads=8):
+    """gss_obs_host: OBS_DTYPE [n_job, n_fix], the code phase and accumulated carrier of every job
+    (rec TRK_REC_DTYPE [n_job, pitch], count [n_job] as tracking returns them) at the samples
+    t_first + k step, k < n_fix"""
+    rec, count = _obs_args(rec, count)
+    obs = np.zeros((len(count), max(int(n_fix), 0)), OBS_DTYPE)
+    _check(lib().gss_obs_host(int(fs_hz), _ptr(rec), rec.shape[1], _ptr(count), len(count),
+                              int(t_first), int(step), int(n_fix), _ptr(obs), threads))
+    return obs
+
+
+class NavData:
+    """gss_navdata: ephemerides and Klobuchar coefficients per PRN, from a RINEX file
+    (NavData(path)) or from decoded subframes alone (NavData())"""
+
+    def __init__(self, rinex=None):
+        self._h = C.c_void_p()
+        if rinex is None:
+            _check(lib().gss_navdata_open_empty(C.byref(self._h)))
+        else:
+            _check(lib().gss_navdata_open_rinex(C.byref(self._h), os.fsencode(rinex)))
+
+    def add_subframe(self, prn, sf):
+        """one NAV_SF_DTYPE element (nav_decode)"""
+        sf = np.ascontiguousarray(sf, NAV_SF_DTYPE).reshape(1)
+        _check(lib().gss_navdata_add_subframe(self._h, int(prn), _ptr(sf)))
+
+    def get(self, prn):
+        """{field: value} of NAVDATA_FIELDS for the ephemeris in use"""
+        f = np.zeros(len(NAVDATA_FIELDS))
+        _check(lib().gss_navdata_get(self._h, int(prn), _ptr(f), len(f)))
+        return dict(zip(NAVDATA_FIELDS, (float(x) for x in f)))
+
+    def range(self, prn, week, sec, xyz, no_iono=False):
+        """gss_pvt_range: (pseudorange [m], its rate [m/s]) the fix's model gives"""
+        xyz = np.ascontiguousarray(xyz, np.float64).reshape(3)
+        out = np.zeros(2)
+        _check(lib().gss_pvt_range(self._h, int(prn), int(week), float(sec), _ptr(xyz),
+                                   int(bool(no_iono)), _ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def close(self):
+        if self._h:
+            lib().gss_navdata_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pvt_solve(navdata, fs, t, sats, no_iono=False, week=0):
+    """gss_pvt_solve: the PvtFix at sample t from sats (PVT_SAT_DTYPE: each satellite's
+    observable at t, its PRN and the epoch and TOW count of one subframe of its job)"""
+    sats = np.ascontiguousarray(sats, PVT_SAT_DTYPE).reshape(-1)
+    fix = PvtFix()
+    opts = _PvtOpts(int(bool(no_iono)), int(week))
+    _check(lib().gss_pvt_solve(navdata._h, float(fs), int(t), _ptr(sats), len(sats),
+                               C.byref(opts), C.byref(fix)))
+    return fix
 
 
 def lut():
@@ -1067,6 +1183,24 @@ class Device:
         _check(lib().gss_track(self._h, C.byref(trk), _ptr(x), n, _ptr(jobs), len(jobs),
                                _ptr(rec), pitch, _ptr(count)))
         return rec, count
+
+    def observables(self, fs_hz, rec_ptr, pitch, count_ptr, n_job, t_first, step, n_fix, obs_ptr,
+                    stream=0):
+        """gss_obs_device: the observables of n_job jobs whose records [n_job, pitch] and counts
+        lie at device pointers (as track() left them) to obs_ptr (n_job x n_fix x 32 bytes, a
+        device pointer).  Asynchronous on stream."""
+        _check(lib().gss_obs_device(self._h, int(fs_hz), C.c_void_p(rec_ptr or None), int(pitch),
+                                    C.c_void_p(count_ptr), int(n_job), int(t_first), int(step),
+                                    int(n_fix), C.c_void_p(obs_ptr or None),
+                                    C.c_void_p(stream or None)))
+
+    def observables_from_host(self, fs_hz, rec, count, t_first, step, n_fix):
+        """gss_obs: observables() on host arrays; returns what observables_host() returns."""
+        rec, count = _obs_args(rec, count)
+        obs = np.zeros((len(count), max(int(n_fix), 0)), OBS_DTYPE)
+        _check(lib().gss_obs(self._h, int(fs_hz), _ptr(rec), rec.shape[1], _ptr(count),
+                             len(count), int(t_first), int(step), int(n_fix), _ptr(obs)))
+        return obs
 
     def run(self, scn, sink, first_block=0, n_blocks=-1, batch=100, threads=8, impair=None,
             jam=None):

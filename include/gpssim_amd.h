@@ -455,6 +455,112 @@ int gss_nav_decode(const gss_trk_rec_t *rec, int64_t n, int64_t skip, gss_nav_sf
    1e-3).  NaN when the moments leave no signal or fewer than two records remain.               */
 double gss_trk_cn0(const gss_trk_rec_t *rec, int64_t n, int64_t skip);
 
+/* ---- observables and position fixes ---------------------------------------------------------------
+   What a receiver reads off its tracking loops (an extension).  A record stores
+   neither the code phase nor the accumulated carrier; both follow exactly from a job's records
+   by prefix sums (csrc/common/gss_obs.h; host, device and tests/obs_oracle.py agree bit for bit).
+     lengths    n_e = s_(e+1) - s_e; the last record's is ceil((M - phi_e) / cs_e) as in tracking
+                (0 when cs_e <= 0 or phi_e outside [0, M), which tracking never writes), with
+                cs_e = cs_nom + dcs_e and M, cs_nom as above
+     prefixes   phi_0 = 0, phi_(e+1) = phi_e + n_e cs_e - M;  A_0 = 0, A_(e+1) = A_e + n_e w_e.
+                A is an int64 modulo 2^64 like W (so is phi, which tracking keeps below cs_e)
+     instant    a sample index t inside epoch e, s_e <= t < s_e + n_e:
+                code = phi_e + (t - s_e) cs_e   [2^-32 chip, below M]
+                adr  = A_e + (t - s_e) w_e      [2^-32 cycle, modulo 2^64]
+                epoch = e, w = w_e.  An instant before the job's first sample, at or past the end
+                of its last epoch, or of a job without records: epoch = -1 and the rest 0
+     instants   t_k = t_first + k step, k < n_fix
+   The records' s must increase; the calls reject n_fix outside 0..2^30, |t_first| > 2^61,
+   step < 1 and a last instant above 2^62.                                                      */
+typedef struct gss_obs {
+    int64_t code;                /* code phase at the instant [2^-32 chip]                      */
+    int64_t adr;                 /* accumulated carrier since the job's start [2^-32 cycle]     */
+    int32_t epoch;               /* the record the instant lies in, or -1                       */
+    int32_t w;                   /* that record's carrier step                                  */
+    int64_t pad;                 /* 0                                                           */
+} gss_obs_t;                     /* 32 bytes                                                    */
+/* rec [n_job][pitch] and count [n_job] as tracking left them (count[j] in 0..pitch), fs_hz the
+   tracking's sample rate; obs [n_job][n_fix]; jobs spread over threads.                        */
+int gss_obs_host(int32_t fs_hz, const gss_trk_rec_t *rec, int64_t pitch, const int32_t *count,
+                 int n_job, int64_t t_first, int64_t step, int32_t n_fix, gss_obs_t *obs,
+                 int threads);
+/* The same on the device: d_rec (8-byte aligned), d_count and d_obs are device pointers, so the
+   records need not leave the device between tracking and this; asynchronous on stream.  A count
+   outside 0..pitch is clamped.  GSS_OBS_PATH=plain takes the plain form of the kernel (one lane
+   walks a job; same bytes).                                                                    */
+int gss_obs_device(gss_dev *d, int32_t fs_hz, const gss_trk_rec_t *d_rec, int64_t pitch,
+                   const int32_t *d_count, int n_job, int64_t t_first, int64_t step,
+                   int32_t n_fix, gss_obs_t *d_obs, void *stream);
+/* gss_obs_device from host buffers: uploads, runs, downloads, synchronises.                    */
+int gss_obs(gss_dev *d, int32_t fs_hz, const gss_trk_rec_t *rec, int64_t pitch,
+            const int32_t *count, int n_job, int64_t t_first, int64_t step, int32_t n_fix,
+            gss_obs_t *obs);
+
+/* Navigation data: per PRN one ephemeris in use and the Klobuchar coefficients, from a RINEX
+   file (every set is kept; a decoded subframe 2 or 3 selects the set with its IODE, and without
+   one a fix takes the set whose clock epoch lies nearest) or from decoded subframes alone
+   (subframes 1-3 with one IODE complete an ephemeris, scaled as IS-GPS-200 table 20-I and 20-III
+   say; subframe 4 page 18 gives the ionosphere).                                               */
+typedef struct gss_navdata gss_navdata;
+int gss_navdata_open_rinex(gss_navdata **h, const char *path);
+int gss_navdata_open_empty(gss_navdata **h);
+/* 0, or GSS_E_ARG; a subframe that says nothing new (ids 4 and 5 but page 18) is accepted        */
+int gss_navdata_add_subframe(gss_navdata *h, int prn, const gss_nav_sf_t *sf);
+/* fields[0 .. n) of GSS_NAVDATA_FIELDS: 0 valid (0 / 1), 1 iode, 2 iodc, 3 toc [s], 4 toe [s],
+   5 af0, 6 af1, 7 af2, 8 tgd, 9 crs, 10 deltan, 11 m0, 12 cuc, 13 ecc, 14 cus, 15 sqrta, 16 cic,
+   17 omg0, 18 cis, 19 inc0, 20 crc, 21 aop, 22 omgdot, 23 idot (radians, not semicircles),
+   24 ionosphere valid, 25..28 alpha, 29..32 beta, 33 week of toe (0 from subframes alone)       */
+#define GSS_NAVDATA_FIELDS 34
+int gss_navdata_get(const gss_navdata *h, int prn, double *fields, int n);
+int gss_navdata_close(gss_navdata *h);
+
+/* The fix.  Each satellite brings its observable at sample t and one anchor: the epoch and TOW
+   count of any subframe decoded from the same job.  Its transmit time of week is
+   6 (tow - 1) + (obs.epoch - sf_epoch) 1e-3 + obs.code / M 1e-3 seconds (the hand-over word
+   counts the next subframe); the receive time is T0 + t / fs with T0, the GPS time of sample 0,
+   unknown.  Iterated least squares over position and T0 in double on the host, against the
+   simulator's own range model (orbit, clock polynomial with the relativistic term and tgd,
+   flight-time and Sagnac rotation, Klobuchar; no troposphere), then velocity and clock drift
+   from the Doppler w fs / 2^32 (sign as the carrier step of tracking).                         */
+#define GSS_PVT_OK        0
+#define GSS_PVT_FEW       1      /* fewer than four usable satellites                           */
+#define GSS_PVT_SINGULAR  2      /* the geometry does not determine a fix                       */
+#define GSS_PVT_DIVERGED  3      /* the iteration did not settle                                */
+typedef struct gss_pvt_sat {
+    gss_obs_t obs;               /* at sample t (epoch -1: the satellite is left out)           */
+    int32_t prn;
+    int32_t sf_epoch;            /* gss_nav_sf_t.epoch of the anchor                            */
+    int32_t sf_tow;              /* its TOW count                                               */
+    int32_t pad;
+} gss_pvt_sat_t;                 /* 48 bytes                                                    */
+typedef struct gss_pvt_opts {
+    int32_t no_iono;             /* 1: the file was made without the ionosphere                 */
+    int32_t week;                /* GPS week of the fix when the navdata does not hold one      */
+} gss_pvt_opts_t;
+typedef struct gss_pvt_fix {
+    double xyz[3];               /* ECEF [m]                                                    */
+    double llh[3];               /* latitude, longitude [rad], height [m]                       */
+    double vel[3];               /* ECEF [m/s]                                                  */
+    double t0_sec;               /* T0: seconds of week ...                                     */
+    double t0_frac;              /* ... as t0_floor + t0_frac, t0_floor a whole second: the     */
+    double t0_floor;             /*     fraction keeps what t0_sec rounds away                  */
+    double drift;                /* receiver clock drift [s/s]                                  */
+    double pdop;
+    double rms;                  /* of the range residuals [m]                                  */
+    int32_t t0_week;
+    int32_t n_used;
+    int32_t status;              /* GSS_PVT_*                                                   */
+    int32_t iterations;
+} gss_pvt_fix_t;                 /* 136 bytes                                                   */
+/* 0 with out->status set (a fix that cannot be made is a status, not an error), or GSS_E_ARG.  */
+int gss_pvt_solve(const gss_navdata *h, double fs, int64_t t, const gss_pvt_sat_t *sats, int n_sat,
+                  const gss_pvt_opts_t *opts, gss_pvt_fix_t *out);
+/* The model the fix inverts: out[0] the pseudorange [m] and out[1] its rate [m/s] of PRN prn at
+   receive time (week, sec) and ECEF position xyz, with the handle's ephemeris in use.
+   GSS_E_STATE when the handle holds none for the PRN.                                          */
+int gss_pvt_range(const gss_navdata *h, int prn, int week, double sec, const double *xyz,
+                  int no_iono, double *out);
+
 /* Kernel timing from HIP events recorded on the launch stream around every Stage A and Stage B
    launch (gss_synth_device, gss_anchor_device, gss_render_device; rings of the last 256 of
    each).  reset!=0 clears the rings (no sync); otherwise waits for the last launches and
