@@ -4,7 +4,9 @@
  * proof that certifies blocks for it (csrc/host/linearize.c) and the CPU checker of the tests
  * (tests/helpers/lin_check.c).  The rows a wave of the kernel starts a segment from (the lines
  * evaluated at the segment start: gss_lin_row_at, gss_lin_chan_of, below) are stated here too,
- * built by the kernel in its set-up and checked on the CPU by tests/helpers/lin_rows.c.
+ * built by the kernel in its set-up and checked on the CPU by tests/helpers/lin_rows.c; so are
+ * the chunk records a wave makes from its row, once for its four chunks (gss_lin_chunk_rec,
+ * checked by tests/helpers/lin_chunk_rec.c).
  *
  * A block's channel is described by two 64-bit integer lines (gss_lin_t): the carrier
  * X(p) = x0 + p*xs mod 2^64 [2^-64 cycle] and the code Z(p) = z0 + p*zs [2^-50 chip, unwrapped]
@@ -230,6 +232,47 @@ GSS_LIN_FN gss_lin_chan gss_lin_chan_of(uint64_t xs, uint64_t zs, uint32_t ca_tb
     c.dq = (uint32_t)((zs * 64u) >> 46);
     c.tab = ca_tbl;
     return c;
+}
+
+/* ---- the chunk records: what a wave's render loop takes per (channel, chunk) ------------------
+   A wave renders its segment in GSS_LIN_SEG / GSS_LIN_CHUNK chunks.  Everything a chunk needs
+   from a channel follows from the channel's segment row, its constants and the chunk index c
+   alone, so gss_lin_kernel makes all of a wave's records in one pass after its set-up (lane
+   16 c + k: chunk c of channel k). */
+#define GSS_LIN_REC_GAIN  1u                   /* flags: the gain changes inside the chunk      */
+#define GSS_LIN_REC_PATCH 2u                   /* flags: the segment holds patched samples      */
+typedef struct {
+    uint64_t B;                  /* the chunk's anchor base: carrier word (high) : code word (low) */
+    uint32_t wa, wn;             /* byte offsets of the window-table rows of this chunk and the
+                                    next (C/A row, code base chip clamped to the table)          */
+    uint32_t flags;              /* GSS_LIN_REC_*                                                */
+    int32_t g;                   /* the signed gain at the chunk's first sample                  */
+} gss_lin_chunk;
+
+/* byte offset of the window-table row of C/A row tab for a chunk whose code base is zb (clamped
+   to the table; gss_lin_win16_ok keeps a certified channel inside it) */
+GSS_LIN_FN uint32_t gss_lin_wrow(uint32_t tab, uint64_t zb)
+{
+    const uint32_t e = (uint32_t)(zb >> 50);
+    return (tab * GSS_LIN_TWE + (e < GSS_LIN_TWE - 1u ? e : GSS_LIN_TWE - 1u)) *
+           (uint32_t)(GSS_LIN_CH * sizeof(uint32_t));
+}
+/* chunk c (0 .. GSS_LIN_SEG / GSS_LIN_CHUNK - 1) of the segment that starts at block sample n0:
+   the bases are the row's advanced by c chunks (c < 4: shifts and adds, mod 2^64 like the lines) */
+GSS_LIN_FN void gss_lin_chunk_rec(const gss_lin_row *row, const gss_lin_chan *chan, int32_t n0,
+                                  int c, gss_lin_chunk *rec)
+{
+    const uint64_t xc = chan->xs * (uint64_t)GSS_LIN_CHUNK, zc = chan->zs * (uint64_t)GSS_LIN_CHUNK;
+    const uint64_t xb = row->x + ((c & 1) ? xc : 0u) + ((c & 2) ? xc << 1 : 0u);
+    const uint64_t zb = row->z + ((c & 1) ? zc : 0u) + ((c & 2) ? zc << 1 : 0u);
+    const int32_t nb0 = n0 + c * GSS_LIN_CHUNK;
+    const int after = row->pos1 <= nb0;                 /* the gain changed before the chunk */
+    const int inside = !after && row->pos1 < nb0 + GSS_LIN_CHUNK;
+    rec->B = (xb & ~0xFFFFFFFFull) | (uint32_t)(zb >> GSS_LIN_CSH);
+    rec->wa = gss_lin_wrow(chan->tab, zb);
+    rec->wn = gss_lin_wrow(chan->tab, zb + zc);
+    rec->flags = (inside ? GSS_LIN_REC_GAIN : 0u) | (row->npatch != 0 ? GSS_LIN_REC_PATCH : 0u);
+    rec->g = after ? row->g01 >> 16 : (int32_t)(int16_t)(row->g01 & 0xFFFF);
 }
 
 /* the kernel's LUT cell and chip at block sample p (128-bit code line; the proof's, on the host

@@ -498,12 +498,17 @@ __global__ __launch_bounds__(SYNTH_THREADS) __attribute__((amdgpu_waves_per_eu(S
    reads of a wave hit a few neighbouring cells and the output leaves as one contiguous 256-B
    (-b 16) store per step.
    A workgroup of 4 waves renders 4 consecutive 4096-sample segments of one block; a wave
-   renders its segment in 4 chunks of LIN_CH = 16 steps of 64 samples.  Per chunk the wave's
-   lanes first write every channel's record in parallel (lin_ct in LDS: the chunk base, the step,
-   the gain operands, the window-table rows to load next); then, two channels at a time, each
-   lane forms its anchors P (code in the low word, carrier in the high word, gss_lin.h) with one
-   64-bit add of the chunk base to its entry of the workgroup's lane table (LDS), and per
-   64-sample step and channel
+   renders its segment in 4 chunks of LIN_CH = 16 steps of 64 samples.  Once per wave, after the
+   set-up's barrier, lane 16 c + k makes the record of chunk c and channel k from the wave's
+   segment row (gss_lin_chunk_rec, gss_lin.h) and writes it to LDS (lin_wrec: per channel the
+   step D, the gain change and its sample; per chunk and channel the base B and, per pair, the
+   two channels' gain operands side by side), followed by the wave's only LDS drain outside the
+   steps; the window-table rows to load ahead stay in two registers of those lanes, which the
+   render loop reads with v_readlane.  The chunk loop keeps no parameter state: a chunk's records
+   are one add from the wave's.  Then per chunk, two channels at a time (one 16-byte read each
+   for the pair's B, D and gain operand), each lane forms its anchors P (code in the low word,
+   carrier in the high word, gss_lin.h) with one 64-bit add of the chunk base to its entry of the
+   workgroup's lane table (LDS), and per 64-sample step and channel
        t = W_s >> byte3(P.lo)  chip sign at bit 0, from the step's window        v_lshrrev_b32_sdwa
        a = alignbit(t, P.hi, 21) & M   LUT byte address: cell (carrier bits 23..31) at bits
                                     2..10, chip sign at bit 11 (second half of the LUT negated)
@@ -565,31 +570,33 @@ typedef float lin_f4 __attribute__((ext_vector_type(4)));
 #define LIN_MAGF  (12582912.0f + 64.0f * LIN_GS)   /* 1.5 2^23 + 64 LIN_GS                       */
 #define LIN_MAGB  0x4B400000u              /* IEEE bits of 1.5 2^23                              */
 
-/* per (block, segment wave, chunk, channel): the chunk's render parameters, built by the wave's
-   lanes in parallel (vector loads and VALU) and read back by the render loop with broadcast LDS
-   reads, so that the scalar unit (one per CU, shared by its four SIMDs) does no per-channel
-   work */
-struct alignas(16) lin_ct {
-    uint64_t B;                  /* the chunk's base (gss_lin.h)                                */
-    uint64_t D;                  /* the 64-sample step dC : dX                                  */
-    int32_t g;                   /* (unused)                                                    */
-    int32_t gd;                  /* gain change inside the chunk (g1 - g0), from sample pos1 on */
-    int32_t pos1;
-    uint32_t flags;              /* 1: a gain change inside the chunk, 2: patched samples       */
-    uint32_t q0, dq, tab;        /* (dq, tab: the channel's window step and C/A row)            */
-    uint32_t wa;                 /* byte offset of the chunk's window-table row                 */
-    uint32_t na, nb;             /* the rows to load while the pair (k, k + 1) renders -- the
-                                    next pair's, the lone last channel's (twice) or the next
-                                    chunk's first pair's (lin_sw_pair); one 8-byte read         */
-    uint32_t wn;                 /* the next chunk's row                                        */
-    uint32_t g2;                 /* the gain as an f16 pair                                     */
-    uint32_t A[5][2];            /* A[i]: the 4x4x4 MFMA's gain operand of lane 4b + i (the gain
-                                    at f16 slot i); A[4] zeros.  The pair MFMA's operand half of
-                                    each lane is A[its class] (lin_pair_cls)                    */
+/* per (block, segment wave): the render parameters of the wave's LIN_CHUNKS chunks, built once by
+   the wave's lanes in parallel (lane 16 c + k: chunk c of channel k, gss_lin_chunk_rec) and read
+   back by the render loop with broadcast LDS reads, so that the scalar unit (one per CU, shared
+   by its four SIMDs) does no per-channel work.  Two channels of a pair lie side by side, so that
+   a pair takes each of B, D and its gain operand with one 16-byte read. */
+#define LIN_CHUNKS (LIN_STEPS / LIN_CH)
+struct alignas(16) lin_ck {                    /* one chunk                                    */
+    uint64_t B[GSS_MAXCH];       /* the chunk's base per channel (gss_lin.h)                    */
+    uint32_t A[GSS_MAXCH / 2][5][4];   /* per pair (2p, 2p + 1) and class i: channel 2p's gain
+                                    operand at words 0, 1 and channel 2p + 1's at words 2, 3.  A
+                                    channel's operand of class i < 4 is the 4x4x4 MFMA's of lane
+                                    4b + i (the gain at f16 slot i), class 4 zeros; the pair
+                                    MFMA's operand of a lane is the entry of its class
+                                    (lin_pair_cls), a lone last channel's its own half          */
 };
-/* the broadcast reads of the record assume these alignments (a misaligned ds_read_b128 is split
+struct alignas(16) lin_wrec {                  /* one wave                                     */
+    uint64_t D[GSS_MAXCH];       /* the 64-sample step dX : dC                                  */
+    int32_t gd[GSS_MAXCH];       /* the segment's gain change (g1 - g0), from sample pos1 on    */
+    int32_t pos1[GSS_MAXCH];
+    lin_ck ck[LIN_CHUNKS];
+};
+static_assert(LIN_CHUNKS * GSS_MAXCH == 64, "one lane per (chunk, channel) record");
+/* the broadcast reads of the records assume these alignments (a misaligned ds_read_b128 is split
    by the hardware and cost the round-4 LDS-window build 3x) */
-static_assert(offsetof(lin_ct, A) % 8 == 0, "lin_ct.A: 8-byte reads");
+static_assert(offsetof(lin_wrec, D) % 16 == 0 && offsetof(lin_wrec, ck) % 16 == 0 &&
+              offsetof(lin_ck, B) % 16 == 0 && offsetof(lin_ck, A) % 16 == 0 &&
+              sizeof(lin_ck) % 16 == 0, "16-byte reads of a pair's B, D and gain operand");
 
 /* the rows a wave starts from -- per (channel, wave segment) the lines at the segment start, per
    channel the step constants -- are gss_lin.h's gss_lin_row and gss_lin_chan: gss_lin_kernel
@@ -659,9 +666,9 @@ __device__ __forceinline__ void lin_wfence(const uint32_t (&ws)[LIN_CH])
                  "s"(ws[12]), "s"(ws[13]), "s"(ws[14]), "s"(ws[15]));
 }
 
-__device__ __forceinline__ lin_wsrc lin_wsrc_of(const lin_ct &t, const uint32_t *__restrict__ tw)
+__device__ __forceinline__ lin_wsrc lin_wsrc_of(uint32_t wa, const uint32_t *__restrict__ tw)
 {
-    const uint32_t off = __builtin_amdgcn_readfirstlane(t.wa);
+    const uint32_t off = __builtin_amdgcn_readfirstlane(wa);
     return lin_wsrc{(const uint32_t *)__builtin_assume_aligned(
         (const char *)tw + off, 64)};
 }
@@ -742,6 +749,7 @@ __device__ __forceinline__ void lin_channel_chunk_m(lin_f4 (&cq)[LIN_CH / 2], li
     uint32_t sw[LIN_CH];
     lin_wissue(W, sw);
     lin_wfence(sw);
+    const int first = pos1 - p0;         /* LANE_GAIN: the lane's steps from 64 s >= first on */
 #pragma unroll
     for (int s = 0; s < LIN_CH; s++) {
         const uint32_t ws = sw[s];
@@ -751,7 +759,7 @@ __device__ __forceinline__ void lin_channel_chunk_m(lin_f4 (&cq)[LIN_CH / 2], li
         const uint32_t a = __builtin_amdgcn_alignbit(t, (uint32_t)(P >> 32), 21) & M;
         uint32_t e = *(const uint32_t *)((const char *)s_lut + a);
         if (LANE_GAIN)
-            e = p0 + s * 64 >= pos1 ? e : 0u;
+            e = s * 64 >= first ? e : 0u;
         if (s & 1) {
             const uint2 bb = make_uint2(e0, e);
             cq[s / 2] = __builtin_amdgcn_mfma_f32_4x4x4f16(A, __builtin_bit_cast(lin_half4, bb),
@@ -765,14 +773,16 @@ __device__ __forceinline__ void lin_channel_chunk_m(lin_f4 (&cq)[LIN_CH / 2], li
 
 /* the lone last channel k of a chunk: its 16 steps from windows ws (SGPRs), one 4x4x4 MFMA per
    two steps */
-__device__ __forceinline__ void lin_sw_steps(lin_f4 (&cq)[LIN_CH / 2], const lin_ct &t, int k,
-                                             int lane, const uint64_t *s_lane, uint32_t M,
+__device__ __forceinline__ void lin_sw_steps(lin_f4 (&cq)[LIN_CH / 2], const lin_wrec *R,
+                                             const lin_ck *T, int k, int lane,
+                                             const uint64_t *s_lane, uint32_t M,
                                              const int32_t *__restrict__ s_lut,
                                              const uint32_t (&ws)[LIN_CH])
 {
-    uint64_t P = s_lane[k * 64 + lane] + t.B;
-    const uint64_t D = t.D;
-    const lin_half4 A = __builtin_bit_cast(lin_half4, *(const uint2 *)t.A[lane & 3]);
+    uint64_t P = s_lane[k * 64 + lane] + T->B[k];
+    const uint64_t D = R->D[k];
+    /* (k is even: the first half of its pair's entry) */
+    const lin_half4 A = __builtin_bit_cast(lin_half4, *(const uint2 *)T->A[k / 2][lane & 3]);
     uint32_t e0 = 0;
 #pragma unroll
     for (int s = 0; s < LIN_CH; s++) {
@@ -792,7 +802,7 @@ __device__ __forceinline__ void lin_sw_steps(lin_f4 (&cq)[LIN_CH / 2], const lin
     }
 }
 
-/* the lane's row of lin_ct.A for the pair MFMA's gain operand: r = lane mod 4 on lanes 20q + r
+/* the lane's class in lin_ck.A for the pair MFMA's gain operand: r = lane mod 4 on lanes 20q + r
    (q, r = 0..3), which hold g_a at element r and g_b at 4 + r; 4 (zeros) elsewhere */
 __device__ __forceinline__ uint32_t lin_pair_cls(int lane)
 {
@@ -801,30 +811,29 @@ __device__ __forceinline__ uint32_t lin_pair_cls(int lane)
 }
 
 /* channels k0, k0 + 1 from the hidden buffers s[68:83], s[84:99] (loaded while the pair before
-   rendered); the next pair's rows (or the lone last channel's) load meanwhile.  FIRST: the
-   chunk's first pair, whose MFMAs take the bias c0 as C (no initialisation moves) */
+   rendered); if load, the two rows to load meanwhile are what lane la (the lane that made
+   channel k0 of this chunk) holds in na and nb: the next pair's, the lone last channel's twice,
+   or the next chunk's first pair's (gss_lin_kernel).  FIRST: the chunk's first pair, whose
+   MFMAs take the bias c0 as C (no initialisation moves) */
 template <bool FIRST>
-__device__ __forceinline__ void lin_sw_pair(lin_f4 (&cq)[LIN_CH / 2], lin_f4 c0, const lin_ct *T, int k0,
-                                            int nc, int lane, const uint64_t *s_lane, uint32_t M,
+__device__ __forceinline__ void lin_sw_pair(lin_f4 (&cq)[LIN_CH / 2], lin_f4 c0, const lin_wrec *R,
+                                            const lin_ck *T, int k0, int lane,
+                                            const uint64_t *s_lane, uint32_t M,
                                             const int32_t *__restrict__ s_lut,
                                             const uint32_t *__restrict__ tw, uint32_t cls,
-                                            bool more)
+                                            uint32_t na, uint32_t nb, int la, bool load)
 {
-    const lin_ct &ta = T[k0], &tb = T[k0 + 1];
-    uint64_t Pa = s_lane[k0 * 64 + lane] + ta.B, Pb = s_lane[(k0 + 1) * 64 + lane] + tb.B;
-    const uint64_t Da = ta.D, Db = tb.D;
-    const uint2 ga = *(const uint2 *)ta.A[cls], gb = *(const uint2 *)tb.A[cls];
-    const lin_half8 A = __builtin_bit_cast(lin_half8, make_uint4(ga.x, ga.y, gb.x, gb.y));
-    /* the rows to load while this pair renders (the record's na, nb): the next pair's (or the
-       lone last channel's), or after the last pair the next chunk's first pair (more: there is a
-       next chunk) */
-    uint32_t na = ta.na, nb = ta.nb;
-    asm volatile("" : "+v"(na), "+v"(nb));       /* read with the record, before the wait below */
+    const uint4 B2 = *(const uint4 *)&T->B[k0], D2 = *(const uint4 *)&R->D[k0];
+    uint64_t Pa = s_lane[k0 * 64 + lane] + (((uint64_t)B2.y << 32) | B2.x);
+    uint64_t Pb = s_lane[(k0 + 1) * 64 + lane] + (((uint64_t)B2.w << 32) | B2.z);
+    const uint64_t Da = ((uint64_t)D2.y << 32) | D2.x, Db = ((uint64_t)D2.w << 32) | D2.z;
+    const lin_half8 A = __builtin_bit_cast(lin_half8, *(const uint4 *)T->A[k0 / 2][cls]);
     uint32_t wsa[LIN_CH], wsb[LIN_CH];
     lin_sw_take_a(wsa);
     lin_sw_take(wsb);
-    if (k0 + 2 < nc || more)
-        lin_sw_load2(tw, na, nb);
+    if (load)
+        lin_sw_load2(tw, (uint32_t)__builtin_amdgcn_readlane((int)na, la),
+                     (uint32_t)__builtin_amdgcn_readlane((int)nb, la));
     uint32_t ea0 = 0, eb0 = 0;
 #pragma unroll
     for (int s = 0; s < LIN_CH; s++) {
@@ -854,7 +863,8 @@ __device__ __forceinline__ void lin_sw_pair(lin_f4 (&cq)[LIN_CH / 2], lin_f4 c0,
 __device__ __forceinline__ lin_half4 lin_gain_operand(uint32_t gh, int lane)
 {
     const uint32_t x = gh << ((lane & 1) * 16);
-    const uint2 v = (lane & 2) ? make_uint2(0u, x) : make_uint2(x, 0u);
+    const uint32_t hi = x & (uint32_t)-((lane >> 1) & 1);        /* x on lanes 4b + 2, 4b + 3 */
+    const uint2 v = make_uint2(x ^ hi, hi);
     return __builtin_bit_cast(lin_half4, v);
 }
 
@@ -1042,7 +1052,7 @@ void gss_lin_kernel(
 {
     __shared__ alignas(16) int32_t s_lut[1024];           /* (cos, sin) f16; [512+i] = -[i] */
     __shared__ uint64_t s_lane[GSS_MAXCH * 64];           /* lane offsets L(l) per channel    */
-    __shared__ lin_ct s_ct[LIN_WAVES][GSS_MAXCH];         /* the current chunk, per wave      */
+    __shared__ lin_wrec s_rec[LIN_WAVES];                 /* the waves' chunk records         */
     __shared__ alignas(16) lin_seg s_seg[LIN_WAVES][GSS_MAXCH];   /* the waves' segment rows  */
     __shared__ alignas(16) lin_chan s_chan[GSS_MAXCH];    /* the block's channel constants    */
     const int b = blockIdx.x / wg_per_blk;
@@ -1106,47 +1116,65 @@ void gss_lin_kernel(
     const int n0 = sg * (64 * LIN_STEPS);
     if (n0 >= n_per_blk)
         return;
-    lin_ct *T = s_ct[wave];
+    const lin_wrec *R = &s_rec[wave];
     uint8_t *ob = out + (size_t)b * block_bytes;
-    bool sw_ahead = false;                 /* the chunk's first pair is already loading */
-    /* ---- lane k: channel k's rows, the same for every chunk of the wave: loaded once, the
-       record's constant fields written once, the lines advanced by one chunk per chunk ---- */
-    uint64_t xb = 0, zb = 0, xs10 = 0, zs10 = 0;       /* chunk bases, per-chunk advances     */
-    int32_t pos1 = INT32_MAX;
-    uint32_t pflag = 0, gh0 = 0, gh1 = 0;
-    uint32_t trow = 0, wa_next = 0;                    /* table row base, this chunk's row     */
-    int g_after = -1;                                  /* the gain the record holds (none yet) */
-    if (lane < nc) {
-        const lin_chan ck = s_chan[lane];
-        const lin_seg sk = s_seg[wave][lane];
-        xb = sk.x;
-        zb = sk.z;
-        xs10 = ck.xs << 10;
-        zs10 = ck.zs << 10;
-        static_assert(64 * LIN_CH == 1024, "one chunk = 2^10 samples");
-        pos1 = sk.pos1;
-        pflag = sk.npatch != 0 ? 2u : 0u;
-        const int g0 = (int)(int16_t)(sk.g01 & 0xFFFF), g1 = sk.g01 >> 16;
-        gh0 = lin_f16_bits(g0 * LIN_GS);
-        gh1 = lin_f16_bits(g1 * LIN_GS);
-        lin_ct &t = T[lane];
-        t.D = ck.d;
-        t.gd = g1 - g0;
-        t.pos1 = sk.pos1;
-        t.dq = ck.dq;
-        t.tab = ck.tab;
-        t.A[4][0] = 0;
-        t.A[4][1] = 0;
-        /* a chunk's row of the window table: its C/A row and code base chip E (clamped to the
-           table; gss_lin_win16_ok keeps a certified channel inside it) */
-        trow = ck.tab * GSS_LIN_TWE;
-        wa_next = (trow + min((uint32_t)(zb >> 50), (uint32_t)(GSS_LIN_TWE - 1))) *
-                  (uint32_t)(LIN_CH * sizeof(uint32_t));
+    /* ---- the wave's chunk records, made once: lane 16 c + k makes chunk c of channel k from the
+       wave's segment row and the channel's constants (gss_lin_chunk_rec); the lanes of channels
+       past nc keep zero rows and flags and store nothing, and the chunks at or past the block's
+       end get records nobody reads.  The chunk loop keeps four registers of the pass, which it
+       takes by v_readlane (no LDS): each lane's window-table row, its flags, and the two rows
+       to load while the pair that starts with the lane's channel renders ---- */
+    uint32_t my_wa = 0, my_flags = 0;
+    const int pk = lane & (GSS_MAXCH - 1), pc = lane / GSS_MAXCH;
+    if (pk < nc) {
+        const lin_chan ck = s_chan[pk];
+        const lin_seg sk = s_seg[wave][pk];
+        gss_lin_chunk r;
+        gss_lin_chunk_rec(&sk, &ck, n0, pc, &r);
+        my_wa = r.wa;
+        my_flags = r.flags;
+        lin_wrec &wr = s_rec[wave];
+        lin_ck &t = wr.ck[pc];
+        t.B[pk] = r.B;
+        /* the channel's half of its pair's entries: lane 4b + i's gain operand, zeros */
+        const uint32_t gh = lin_f16_bits(r.g * LIN_GS);
+        uint32_t (&A)[5][4] = t.A[pk / 2];
+        const int h = 2 * (pk & 1);
+        *(uint2 *)&A[0][h] = make_uint2(gh, 0u);
+        *(uint2 *)&A[1][h] = make_uint2(gh << 16, 0u);
+        *(uint2 *)&A[2][h] = make_uint2(0u, gh);
+        *(uint2 *)&A[3][h] = make_uint2(0u, gh << 16);
+        *(uint2 *)&A[4][h] = make_uint2(0u, 0u);
+        if (pc == 0) {                                 /* the channel's part, once */
+            wr.D[pk] = ck.d;
+            wr.gd[pk] = (sk.g01 >> 16) - (int)(int16_t)(sk.g01 & 0xFFFF);
+            wr.pos1[pk] = sk.pos1;
+        }
     }
+    /* the rows to load while the pair (k, k + 1) renders: the next pair's, the lone last
+       channel's (twice), or after the last pair -- and for a lone last channel itself -- the
+       next chunk's first pair's (the lone first channel's twice); gathered once from the lanes
+       that hold them (the last chunk's wrap to the first: never loaded) */
+    uint32_t my_na, my_nb;
+    {
+        const bool in2 = pk + 2 < nc, in3 = pk + 3 < nc;
+        const int nxt = (pc * GSS_MAXCH + GSS_MAXCH) & 63;
+        const int sa = in2 ? lane + 2 : nxt;
+        const int sb = in3 ? lane + 3 : in2 ? lane + 2 : nxt + (nc > 1 ? 1 : 0);
+        my_na = (uint32_t)__builtin_amdgcn_ds_bpermute(sa << 2, (int)my_wa);
+        my_nb = (uint32_t)__builtin_amdgcn_ds_bpermute(sb << 2, (int)my_wa);
+    }
+    /* the channels with a gain change or patches, 16 bits per chunk (wave-uniform) */
+    const uint64_t fmask = __builtin_amdgcn_ballot_w64(my_flags != 0);
+    wave_sync_lds();
+    /* the first chunk's first pair's rows; every later chunk's load during the chunk before */
+    if (nc > 0)
+        lin_sw_load2(tw, (uint32_t)__builtin_amdgcn_readlane((int)my_wa, 0),
+                     (uint32_t)__builtin_amdgcn_readlane((int)my_wa, nc > 1 ? 1 : 0));
 
     const int nc_blk = nc;
-    for (int c = 0; c < LIN_STEPS / LIN_CH; c++) {
-        /* the channel count made opaque per chunk: its conditions (nc > 1, lane + 2 < nc, ...)
+    for (int c = 0; c < LIN_CHUNKS; c++) {
+        /* the channel count made opaque per chunk: its conditions (nc > 1, k0 + 2 < nc, ...)
            are recomputed by the scalar unit and one compare each, instead of being hoisted out
            of the loop, spilled to VGPR lanes and read back with 12 v_readlane per chunk */
         int nc = nc_blk;
@@ -1154,68 +1182,14 @@ void gss_lin_kernel(
         const int nb0 = n0 + c * (64 * LIN_CH);           /* first sample of the chunk */
         if (nb0 >= n_per_blk)
             break;
-        /* ---- the chunk's parameters, lane k for channel k: computed on every lane (the
-           lanes past nc hold zero rows and flags, their values unused), stored by the first nc
-           (no phi moves for the lanes outside) ---- */
-        const bool after = pos1 <= nb0;                    /* the data bit changed before it */
-        const bool chg = pos1 < nb0 + 64 * LIN_CH;         /* ... or changes inside it      */
-        const uint32_t my_flags = (chg && !after ? 1u : 0u) | pflag;
-        const uint64_t zn = zb + zs10;                     /* the next chunk's code base */
-        const uint32_t my_wa = wa_next;
-        const uint32_t my_wn = (trow + min((uint32_t)(zn >> 50), (uint32_t)(GSS_LIN_TWE - 1))) *
-                               (uint32_t)(LIN_CH * sizeof(uint32_t));
-        if (lane < nc) {
-            lin_ct &t = T[lane];
-            /* the chunk's base B (gss_lin.h): the segment's lines plus c chunks */
-            t.B = (xb & ~0xFFFFFFFFull) | (uint32_t)(zb >> GSS_LIN_CSH);
-            t.flags = my_flags;
-            t.wa = my_wa;
-            t.wn = my_wn;
-            if ((int)after != g_after) {                   /* the gain the chunk starts with */
-                g_after = (int)after;
-                const uint32_t gh = after ? gh1 : gh0;
-                t.A[0][0] = gh;         t.A[0][1] = 0;     /* lane 4b + i's gain operand */
-                t.A[1][0] = gh << 16;   t.A[1][1] = 0;
-                t.A[2][0] = 0;          t.A[2][1] = gh;
-                t.A[3][0] = 0;          t.A[3][1] = gh << 16;
-                t.g2 = gh | (gh << 16);
-            }
-        }
-        wa_next = my_wn;
-        xb += xs10;
-        zb = zn;
-        /* the channels with a gain change or patches in this chunk (wave-uniform) */
-        /* the first two channels' rows of this chunk and the next (scalar: readlane) */
-        const uint32_t wa0 = (uint32_t)__builtin_amdgcn_readlane((int)my_wa, 0);
-        const uint32_t wa1r = (uint32_t)__builtin_amdgcn_readlane((int)my_wa, 1);
-        const uint32_t wn0 = (uint32_t)__builtin_amdgcn_readlane((int)my_wn, 0);
-        const uint32_t wn1r = (uint32_t)__builtin_amdgcn_readlane((int)my_wn, 1);
-        const uint32_t wa1 = nc > 1 ? wa1r : wa0, wn1 = nc > 1 ? wn1r : wn0;
-        {
-            /* the rows each pair (k, k + 1) loads ahead (gather from lanes k + 2, k + 3, 0, 1:
-               once per chunk in parallel, instead of selects per pair); the channels are lanes
-               0..15, one DPP row: lane k takes lane k + 2's / k + 3's by a row shift (row_shl),
-               the first pair's by readlane -- no LDS permutes */
-            const uint32_t wa2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)my_wa, 0x102, 0xF,
-                                                                       0xF, true);
-            const uint32_t wa3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)my_wa, 0x103, 0xF,
-                                                                       0xF, true);
-            if (lane < nc) {
-                const bool in2 = lane + 2 < nc, in3 = lane + 3 < nc;
-                T[lane].na = in2 ? wa2 : wn0;
-                T[lane].nb = in3 ? wa3 : in2 ? wa2 : wn1;
-            }
-        }
-        const uint64_t fmask = __builtin_amdgcn_ballot_w64(my_flags != 0);
-        wave_sync_lds();
+        const lin_ck *T = &R->ck[c];
+        const int l0 = c * GSS_MAXCH;          /* lane l0 + k made the chunk's channel k */
         lin_f4 acc[LIN_CH / 2];
-        /* the first pair's rows: loaded during the chunk before, or now */
-        if (nc > 0 && !sw_ahead)
-            lin_sw_load2(tw, wa0, wa1);
-        const bool more = c + 1 < LIN_STEPS / LIN_CH && nb0 + 64 * LIN_CH < n_per_blk;
+        const bool more = c + 1 < LIN_CHUNKS && nb0 + 64 * LIN_CH < n_per_blk;
         int k0 = 0;
         if (nc >= 2) {                                    /* the first pair sets acc = bias + ... */
-            lin_sw_pair<true>(acc, c0, T, 0, nc, lane, s_lane, M, s_lut, tw, cls, more);
+            lin_sw_pair<true>(acc, c0, R, T, 0, lane, s_lane, M, s_lut, tw, cls, my_na, my_nb, l0,
+                              2 < nc || more);
             k0 = 2;
         } else {
             /* (the copies pinned inside this branch: hoisted, they cost 32 moves every chunk) */
@@ -1231,7 +1205,8 @@ void gss_lin_kernel(
         for (int p = 1; p < GSS_MAXCH / 2; p++) {
             if (2 * p + 1 >= nc)
                 break;
-            lin_sw_pair<false>(acc, c0, T, 2 * p, nc, lane, s_lane, M, s_lut, tw, cls, more);
+            lin_sw_pair<false>(acc, c0, R, T, 2 * p, lane, s_lane, M, s_lut, tw, cls, my_na, my_nb,
+                               l0 + 2 * p, 2 * p + 2 < nc || more);
             k0 = 2 * p + 2;
         }
         if (k0 < nc) {                                    /* the lone last channel: s[68:83] */
@@ -1240,35 +1215,26 @@ void gss_lin_kernel(
             lin_sw_take(wb);                              /* (its duplicate, unused) */
             (void)wb;
             if (more)                                     /* the next chunk's first pair */
-                lin_sw_load2(tw, wn0, wn1);
-            lin_sw_steps(acc, T[k0], k0, lane, s_lane, M, s_lut, ws);
-            k0 = nc;
-        }
-        sw_ahead = nc > 0 && more;
-        for (int k = k0; k < nc; k++) {                   /* (none left: k0 == nc) */
-            const lin_ct &t = T[k];
-            const uint64_t B = t.B, D = t.D;
-            const uint2 a2 = *(const uint2 *)t.A[lane & 3];
-            lin_channel_chunk_m<false>(acc, c0, s_lane[k * 64 + lane] + B, D, lin_wsrc_of(t, tw), M,
-                                       __builtin_bit_cast(lin_half4, a2), 0, 0, s_lut);
+                lin_sw_load2(tw, (uint32_t)__builtin_amdgcn_readlane((int)my_na, l0 + k0),
+                             (uint32_t)__builtin_amdgcn_readlane((int)my_nb, l0 + k0));
+            lin_sw_steps(acc, R, T, k0, lane, s_lane, M, s_lut, ws);
         }
         /* gain changes and patches (rare): only the channels whose flags are set */
-        for (uint64_t fm = fmask; fm; fm &= fm - 1) {
-            const int k = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(fm));
-            const lin_ct &t = T[k];
-            const uint64_t B = t.B, D = t.D;
-            const uint32_t fl = __builtin_amdgcn_readfirstlane(t.flags);
-            if (__builtin_expect(fl & 1u, 0)) {
+        for (uint32_t fm = (uint32_t)(fmask >> l0) & ((1u << GSS_MAXCH) - 1u); fm; fm &= fm - 1) {
+            const int k = __builtin_amdgcn_readfirstlane(__builtin_ctz(fm));
+            const uint32_t fl = (uint32_t)__builtin_amdgcn_readlane((int)my_flags, l0 + k);
+            if (__builtin_expect(fl & GSS_LIN_REC_GAIN, 0)) {
+                const uint32_t wa = (uint32_t)__builtin_amdgcn_readlane((int)my_wa, l0 + k);
                 uint32_t l2 = (uint32_t)lane;
                 asm volatile("" : "+v"(l2));
-                lin_channel_chunk_m<true>(acc, c0, s_lane[k * 64 + l2] + B, D, lin_wsrc_of(t, tw), M,
-                                          lin_gain_operand(lin_f16_bits(t.gd * LIN_GS), (int)l2), t.pos1,
-                                          nb0 + (int)l2, s_lut);
+                lin_channel_chunk_m<true>(acc, c0, s_lane[k * 64 + l2] + T->B[k], R->D[k],
+                                          lin_wsrc_of(wa, tw), M,
+                                          lin_gain_operand(lin_f16_bits(R->gd[k] * LIN_GS), (int)l2),
+                                          R->pos1[k], nb0 + (int)l2, s_lut);
             }
-            if (__builtin_expect(fl & 2u, 0))
+            if (__builtin_expect(fl & GSS_LIN_REC_PATCH, 0))
                 lin_patch_fix(acc, L + k, nb0, lane);
         }
-        wave_sync_lds();                                  /* T is rewritten by the next chunk */
         if (nb0 + 64 * LIN_CH <= n_per_blk)
             lin_store<FMT, false>(acc, ob, nb0, lane, n_per_blk);
         else
