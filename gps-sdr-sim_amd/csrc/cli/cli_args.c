@@ -97,6 +97,45 @@ bad:
     return 1;
 }
 
+/* One --multipath value into c->echo[c->n_echo]:
+     <prn|all>,<delay_m>,<atten_db>[,<phase_deg>[,<doppler_hz>]]
+   at the rate the run uses (a multiple of 10 Hz, gpssim.c:1877-1881), by gss_echo_make. */
+static int echo_option(gss_cli_t *c, const char *val)
+{
+    char buf[256], *f[6];
+    int nf = 0;
+    if (strlen(val) >= sizeof buf)
+        goto bad;
+    strcpy(buf, val);
+    for (char *p = buf;; p++) {
+        if (nf == 6)
+            goto bad;
+        f[nf++] = p;
+        p = strchr(p, ',');
+        if (!p)
+            break;
+        *p = '\0';
+    }
+    if (nf < 3 || nf > 5)
+        goto bad;
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};             /* prn delay_m atten_db phase_deg doppler_hz */
+    if (strcmp(f[0], "all") != 0 &&
+        (parse_real(f[0], &v[0]) || v[0] < 1.0 || v[0] > 32.0 || v[0] != floor(v[0])))
+        goto bad;
+    for (int i = 1; i < nf; i++)
+        if (parse_real(f[i], &v[i]))
+            goto bad;
+    const double fs = floor(c->opt.samp_freq / 10.0) * 10.0;
+    if (gss_echo_make(fs, (int)v[0], v[1], v[2], v[3], v[4], &c->echo[c->n_echo]))
+        goto bad;
+    c->n_echo++;
+    return 0;
+bad:
+    fprintf(stderr, "ERROR: Invalid multipath echo (<prn|all>,<delay_m>,<atten_db>[,<phase_deg>"
+                    "[,<doppler_hz>]]: PRN 1..32, delay 0..299.8 km, at most 12 dB of gain).\n");
+    return 1;
+}
+
 /* The noise options into c->impair.
      --cn0=<dB-Hz>        sigma = 250 sqrt(fs / (2 10^(cn0/10))) LSB per component: 250 is the carrier
                           table's amplitude, so this is the C/N0 of a satellite at gain 128 (path
@@ -105,11 +144,12 @@ bad:
      --noise-sigma=<LSB>  sigma directly
      --noise-shift=<s>    0..8, or auto (default): the least s with (4 sigma + 2047 + J) / 2^s <=
                           R, R = 32767 for -b 16 and 2047 for -b 8 (what >> 4 takes to the 8-bit
-                          range), J = sum of the jammers' amp 250 / 65536 (0 without --jam); 0 for
-                          -b 1, which keeps only the sign
+                          range), J = sum of the jammers' amp 250 / 65536 (0 without --jam) plus
+                          2047 alpha_q16 / 65536 per echo (--multipath); 0 for -b 1, which keeps
+                          only the sign
      --seed=<u64>         default 0
-   With --jam and neither --cn0 nor --noise-sigma: sigma 0 (--noise-shift is then accepted,
-   --seed is not). */
+   With --jam or --multipath and neither --cn0 nor --noise-sigma: sigma 0 (--noise-shift is then
+   accepted, --seed is not). */
 static int noise_options(gss_cli_t *c, const char *o_cn0, const char *o_sigma, const char *o_shift,
                          const char *o_seed)
 {
@@ -118,16 +158,16 @@ static int noise_options(gss_cli_t *c, const char *o_cn0, const char *o_sigma, c
         return 1;
     }
     if (!o_cn0 && !o_sigma) {
-        if (o_seed || (o_shift && c->n_jam == 0)) {
+        if (o_seed || (o_shift && c->n_jam == 0 && c->n_echo == 0)) {
             fprintf(stderr, "ERROR: --noise-shift and --seed need --cn0 or --noise-sigma.\n");
             return 1;
         }
-        if (c->n_jam == 0)
+        if (c->n_jam == 0 && c->n_echo == 0)
             return 0;
     }
     double v = 0.0, q8 = 0.0;
     if (!o_cn0 && !o_sigma) {
-        /* jammers alone: no noise */
+        /* jammers or echoes alone: no noise */
     } else if (o_cn0) {
         if (parse_real(o_cn0, &v) || v < -100.0 || v > 200.0) {
             fprintf(stderr, "ERROR: Invalid C/N0.\n");
@@ -157,6 +197,8 @@ static int noise_options(gss_cli_t *c, const char *o_cn0, const char *o_sigma, c
         double peak = 4.0 * (q8 / 256.0) + 2047.0;
         for (int i = 0; i < c->n_jam; i++)
             peak += (double)c->jam[i].amp * 250.0 / 65536.0;
+        for (int i = 0; i < c->n_echo; i++)
+            peak += 2047.0 * (double)c->echo[i].alpha_q16 / 65536.0;
         const double room = c->opt.data_format == GSS_FMT_SC16 ? 32767.0 : 2047.0;
         int s = 0;
         while (c->opt.data_format != GSS_FMT_SC01 && s < 8 && peak > room * (double)(1 << s))
@@ -201,7 +243,18 @@ int gss_cli_parse(int argc, char **argv, gss_cli_t *c)
     /* jammers (--jam=..., repeatable): resolved with them, in the order given */
     const char *o_jam[GSS_MAXJAM];
     int n_ojam = 0;
+    /* multipath echoes (--multipath=..., repeatable): the same */
+    const char *o_echo[GSS_MAXECHO];
+    int n_oecho = 0;
     for (int i = 0; i < argc; i++) {
+        if (i > 0 && strncmp(argv[i], "--multipath=", 12) == 0) {
+            if (n_oecho == GSS_MAXECHO) {
+                fprintf(stderr, "ERROR: At most %d multipath echoes.\n", GSS_MAXECHO);
+                return 1;
+            }
+            o_echo[n_oecho++] = argv[i] + 12;
+            continue;
+        }
         if (i > 0 && strncmp(argv[i], "--jam=", 6) == 0) {
             if (n_ojam == GSS_MAXJAM) {
                 fprintf(stderr, "ERROR: At most %d jammers.\n", GSS_MAXJAM);
@@ -341,6 +394,9 @@ int gss_cli_parse(int argc, char **argv, gss_cli_t *c)
     }
     for (int i = 0; i < n_ojam; i++)
         if (jam_option(c, o_jam[i]))
+            return 1;
+    for (int i = 0; i < n_oecho; i++)
+        if (echo_option(c, o_echo[i]))
             return 1;
     return noise_options(c, o_cn0, o_sigma, o_shift, o_seed);
 }

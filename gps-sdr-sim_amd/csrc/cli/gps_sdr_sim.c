@@ -331,7 +331,8 @@ static int run_rank(const gss_cli_t *cli, gss_scn *scn, const gss_scn_info_t *in
     /* the noise does not change the carriers, so the hand-off stays as it is */
     gss_run_opts_t ro = {handoff ? handoff_in : NULL, handoff ? handoff_out : NULL, &h,
                          handoff && spec ? handoff_predict : NULL,
-                         cli->has_impair ? &cli->impair : NULL, cli->jam, cli->n_jam};
+                         cli->has_impair ? &cli->impair : NULL, cli->jam, cli->n_jam,
+                         cli->echo, cli->n_echo};
     if (run_id && *run_id) {
         if (rank > 0)
             snprintf(h.in_path, sizeof h.in_path, "%s.gss-carr-%s-%lld", cli->out_file, run_id,
@@ -388,6 +389,10 @@ int main(int argc, char **argv)
         fprintf(stderr, "Jammer %d: step0 = %llu, rate = %llu, sweep = %u, amp = %u, gate = %u / %u\n",
                 i, (unsigned long long)cli.jam[i].step0, (unsigned long long)cli.jam[i].rate,
                 cli.jam[i].sweep, cli.jam[i].amp, cli.jam[i].gate_on, cli.jam[i].gate_period);
+    for (int i = 0; i < cli.n_echo && rank == 0; i++)
+        fprintf(stderr, "Echo %d: prn = %d, delay = %llu, alpha_q16 = %u, theta0 = %llu, dstep = %llu\n",
+                i, cli.echo[i].prn, (unsigned long long)cli.echo[i].delay, cli.echo[i].alpha_q16,
+                (unsigned long long)cli.echo[i].theta0, (unsigned long long)cli.echo[i].dstep);
     if (world > 1)
         return run_rank(&cli, scn, &info, rank, world);
 
@@ -416,6 +421,8 @@ int main(int argc, char **argv)
     ro.impair = &cli.impair;
     ro.jam = cli.jam;
     ro.n_jam = cli.n_jam;
+    ro.echo = cli.echo;
+    ro.n_echo = cli.n_echo;
     if (gss_run_ex(dev, scn, 0, -1, batch, threads, write_sink, fp,
                    cli.has_impair ? &ro : NULL)) {
         fprintf(stderr, "\nERROR: %s\n", gss_last_error());

@@ -76,6 +76,7 @@
 extern "C" int gss_fail(int code, const char *fmt, ...);
 extern "C" void gss_pool_select(int id);             /* pool.c */
 extern "C" int gss_jam_check(const gss_jam_t *jam, int n_jam);   /* jam.c */
+extern "C" int gss_echo_check(const gss_echo_t *echo, int n_echo);   /* echo.c */
 /* n bytes from src to dst by a copy kernel on st: pinned host or device memory on either side
    (gss_producers.hip; not exported) */
 int run_copy_launch(void *dst, const void *src, size_t n, hipStream_t st);
@@ -91,6 +92,13 @@ extern "C" __attribute__((weak)) int gss_jam_device(gss_dev *d, const gss_impair
                                                     const gss_jam_t *jam, int n_jam,
                                                     const int16_t *iq, uint64_t sample0, size_t n,
                                                     int fmt, void *out, void *stream);
+/* ... and the echoes' (gss_echo.hip), which runs before either in a run with echoes */
+extern "C" __attribute__((weak)) int gss_echo_device(gss_dev *d, const gss_echo_t *echo, int n_echo,
+                                                     const gss_chan_blk_t *blk, const int32_t *nch,
+                                                     int nblk, int n_per_blk,
+                                                     const uint32_t *ca_bits, int n_ca,
+                                                     const uint32_t *nav, int n_nav,
+                                                     uint64_t sample0, int16_t *iq, void *stream);
 
 #define RUN_TRY(x)                                                                           \
     do {                                                                                     \
@@ -412,6 +420,8 @@ struct Run {
                                                render at SC16 and the impairment writes fmt_out */
     gss_jam_t jam[GSS_MAXJAM];              /* the run's copy of opts->jam */
     int n_jam = 0;
+    gss_echo_t echo[GSS_MAXECHO];           /* the run's copy of opts->echo */
+    int n_echo = 0;
     int fmt_out = 0;                 /* the scenario's format: what the sink receives          */
     /* with opts->carr_in: the whole range planned up front (rows, carriers, checkpoints) */
     std::vector<gss_chan_blk_t> pre_blk;
@@ -1382,6 +1392,15 @@ int impair_blocks(Run &r, Slot &sl, int b0, int nblk, hipStream_t st)
     uint8_t *in = sl.d_out + 4 * n * (size_t)b0;
     uint8_t *out = sl.d_imp ? sl.d_imp + gss_block_bytes(r.n_per_blk, r.fmt_out) * (size_t)b0 : in;
     const uint64_t s0 = (uint64_t)(sl.first + b0) * (uint64_t)n;
+    if (r.n_echo > 0) {                     /* the echoes first, on the render and its rows */
+        const SlotDev v = slot_dev(sl);
+        const int n_rows = sl.nav_first + sl.n_nav;
+        const int rc = gss_echo_device(r.dev, r.echo, r.n_echo, v.blk + (size_t)b0 * GSS_MAXCH,
+                                       v.nch + b0, nblk, r.n_per_blk, r.d_ca, 32, r.d_nav,
+                                       n_rows > 0 ? n_rows : 1, s0, (int16_t *)in, st);
+        if (rc)
+            return rc;
+    }
     if (r.n_jam > 0)
         return gss_jam_device(r.dev, r.impair, r.jam, r.n_jam, (const int16_t *)in, s0,
                               n * (size_t)nblk, r.fmt_out, out, st);
@@ -2003,6 +2022,15 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
     if (n_jam > 0 && !gss_jam_device)
         return gss_fail(GSS_E_STATE, "jammers requested, but this build has no jammer launch "
                                      "(gss_jam_device)");
+    const int n_echo = opts ? opts->n_echo : 0;
+    if (n_echo < 0 || n_echo > GSS_MAXECHO || (n_echo > 0 && (!imp || !opts->echo)))
+        return gss_fail(GSS_E_ARG, "invalid echoes (0..%d of them, with an impairment for the "
+                                   "shift)", GSS_MAXECHO);
+    if (n_echo > 0 && (rc = gss_echo_check(opts->echo, n_echo)) != 0)
+        return rc;
+    if (n_echo > 0 && !gss_echo_device)
+        return gss_fail(GSS_E_STATE, "echoes requested, but this build has no echo launch "
+                                     "(gss_echo_device)");
     const size_t bb_r = imp ? (size_t)info.n_per_blk * 4 : bb;
     if (batch <= 0)
         batch = 100;
@@ -2024,6 +2052,9 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
     r.n_jam = n_jam;
     for (int i = 0; i < n_jam; i++)
         r.jam[i] = opts->jam[i];
+    r.n_echo = n_echo;
+    for (int i = 0; i < n_echo; i++)
+        r.echo[i] = opts->echo[i];
     r.fmt = imp ? GSS_FMT_SC16 : info.data_format;
     r.fmt_out = info.data_format;
     r.bb = bb;

@@ -164,6 +164,24 @@ class Jam(C.Structure):
                 f"gate_on={self.gate_on}, gate_shift={self.gate_shift}, pad={self.pad})")
 
 
+MAXECHO = 4                                        # GSS_MAXECHO
+
+
+class Echo(C.Structure):
+    """gss_echo_t: one multipath echo in the definition's integers (include/gpssim_amd.h);
+    echo_make() fills one from physical parameters."""
+    _fields_ = [("delay", C.c_uint64), ("theta0", C.c_uint64), ("dstep", C.c_uint64),
+                ("alpha_q16", C.c_uint32), ("prn", C.c_int32)]
+
+    def __init__(self, delay=0, theta0=0, dstep=0, alpha_q16=65536, prn=0):
+        m = 2**64 - 1
+        super().__init__(int(delay) & m, int(theta0) & m, int(dstep) & m, int(alpha_q16), int(prn))
+
+    def __repr__(self):
+        return (f"Echo(delay={self.delay}, theta0={self.theta0}, dstep={self.dstep}, "
+                f"alpha_q16={self.alpha_q16}, prn={self.prn})")
+
+
 class Acq(C.Structure):
     """gss_acq_t: an acquisition search.  fs_hz, fmt (16 / 8 / 1), coh_ms x n_coh windows, bins
     -n_half..n_half of bin_hz (default 500 / coh_ms), qshift (-1: auto), prns (iterable of 1..32,
@@ -241,13 +259,15 @@ class _Truth(C.Structure):                           # gss_acq_truth_t
 class _Cli(C.Structure):
     _fields_ = [("opt", _Opts), ("nav_file", C.c_char * 256), ("motion_file", C.c_char * 256),
                 ("out_file", C.c_char * 256), ("impair", Impair), ("has_impair", C.c_int),
-                ("jam", Jam * MAXJAM), ("n_jam", C.c_int)]
+                ("jam", Jam * MAXJAM), ("n_jam", C.c_int),
+                ("echo", Echo * MAXECHO), ("n_echo", C.c_int)]
 
 
 class _RunOpts(C.Structure):                         # gss_run_opts_t
     _fields_ = [("carr_in", C.c_void_p), ("carr_out", C.c_void_p), ("carr_user", C.c_void_p),
                 ("carr_predict", C.c_void_p), ("impair", C.POINTER(Impair)),
-                ("jam", C.POINTER(Jam)), ("n_jam", C.c_int)]
+                ("jam", C.POINTER(Jam)), ("n_jam", C.c_int),
+                ("echo", C.POINTER(Echo)), ("n_echo", C.c_int)]
 
 
 class _Info(C.Structure):
@@ -298,6 +318,12 @@ _SIGS = {
                                C.c_size_t, C.c_int, _P]),
     "gss_jam_device": (C.c_int, [_P, C.POINTER(Impair), C.POINTER(Jam), C.c_int, _P, C.c_uint64,
                                  C.c_size_t, C.c_int, _P, _P]),
+    "gss_echo_make": (C.c_int, [C.c_double, C.c_int] + [C.c_double] * 4 + [C.POINTER(Echo)]),
+    "gss_echo_check": (C.c_int, [C.POINTER(Echo), C.c_int]),
+    "gss_echo_host": (C.c_int, [C.POINTER(Echo), C.c_int, _P, _P, C.c_int, C.c_int, _P, C.c_int,
+                                _P, C.c_int, C.c_uint64, _P]),
+    "gss_echo_device": (C.c_int, [_P, C.POINTER(Echo), C.c_int, _P, _P, C.c_int, C.c_int, _P,
+                                  C.c_int, _P, C.c_int, C.c_uint64, _P, _P]),
     "gss_acq_sizes": (C.c_int, [C.POINTER(Acq), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32)]),
@@ -497,6 +523,42 @@ def jam_host(imp, jam, iq, sample0, fmt):
     arr, nj = _jam_array(jam)
     _check(lib().gss_jam_host(C.byref(imp), arr, nj, _ptr(iq), int(sample0), n, int(fmt),
                               _ptr(out)))
+    return out
+
+
+def _echo_array(echo):
+    """(ctypes array or None, count) of an iterable of Echo; the count is passed on as it is, so
+    that the library refuses more than MAXECHO"""
+    echo = list(echo or ())
+    return ((Echo * len(echo))(*echo) if echo else None), len(echo)
+
+
+def echo_make(fs_hz, prn, delay_m, atten_db, phase_deg=0.0, doppler_hz=0.0):
+    """An Echo from physical parameters (gss_echo_make): of satellite prn (0: of every one), the
+    extra path delay_m in metres, atten_db below the direct signal, its carrier phase_deg against
+    the direct signal's at sample 0 and its own doppler_hz (fading) at the rate fs_hz."""
+    e = Echo()
+    _check(lib().gss_echo_make(float(fs_hz), int(prn), float(delay_m), float(atten_db),
+                               float(phase_deg), float(doppler_hz), C.byref(e)))
+    return e
+
+
+def echo_host(echo, blk, nch, ca, nav, n_per_blk, sample0, iq):
+    """gss_echo_host: the echoes `echo` (an iterable of Echo) of the rows blk [nblk][MAXCH], nch
+    [nblk] (tables ca, nav) added to their SC16 render iq (int16, 2 * nblk * n_per_blk); returns
+    a new array, iq is left as it is."""
+    blk = np.ascontiguousarray(blk, CHAN_DTYPE)
+    nch = np.ascontiguousarray(nch, np.int32)
+    ca = np.ascontiguousarray(ca, np.uint32)
+    nav = np.ascontiguousarray(nav, np.uint32)
+    out = np.array(iq, np.int16).reshape(-1)
+    nblk = len(nch)
+    if blk.size != nblk * MAXCH or out.size != 2 * nblk * int(n_per_blk):
+        raise ValueError("echo_host: blk, nch and iq do not describe the same blocks")
+    arr, ne = _echo_array(echo)
+    _check(lib().gss_echo_host(arr, ne, _ptr(blk), _ptr(nch), nblk, int(n_per_blk), _ptr(ca),
+                               ca.size // CA_WORDS, _ptr(nav), nav.size // NAV_WORDS,
+                               int(sample0), _ptr(out)))
     return out
 
 
@@ -799,10 +861,13 @@ class Scenario:
             self.impair = Impair(cli.impair.sigma_q8, cli.impair.shift, cli.impair.seed)
         if cli.n_jam:                                  # --jam (Device.run(jam=))
             self.jam = [Jam.from_buffer_copy(cli.jam[i]) for i in range(cli.n_jam)]
+        if cli.n_echo:                                 # --multipath (Device.run(echo=))
+            self.echo = [Echo.from_buffer_copy(cli.echo[i]) for i in range(cli.n_echo)]
         return self, cli.out_file.decode()
 
     impair = None                # the command line's noise options (from_cli), else None
     jam = None                   # the command line's jammers (from_cli: a list of Jam), else None
+    echo = None                  # the command line's echoes (from_cli: a list of Echo), else None
 
     def _init_info(self):
         inf = _Info()
@@ -1146,6 +1211,17 @@ class Device:
                                     int(sample0), int(n), int(fmt), C.c_void_p(out_ptr),
                                     C.c_void_p(stream or None)))
 
+    def echo_device(self, echo, blk_ptr, nch_ptr, nblk, n_per_blk, ca_ptr, n_ca, nav_ptr, n_nav,
+                    sample0, iq_ptr, stream=0):
+        """gss_echo_device: the echoes `echo` (an iterable of Echo) added in place to the SC16
+        render at device pointer iq_ptr (nblk * n_per_blk samples) of the device rows blk_ptr,
+        nch_ptr with the device tables ca_ptr, nav_ptr; asynchronous on stream."""
+        arr, ne = _echo_array(echo)
+        _check(lib().gss_echo_device(self._h, arr, ne, C.c_void_p(blk_ptr), C.c_void_p(nch_ptr),
+                                     int(nblk), int(n_per_blk), C.c_void_p(ca_ptr), int(n_ca),
+                                     C.c_void_p(nav_ptr), int(n_nav), int(sample0),
+                                     C.c_void_p(iq_ptr), C.c_void_p(stream or None)))
+
     def acquire(self, acq, samples_ptr, peaks_ptr, grid_ptr=0, qshift_ptr=0, stream=0):
         """gss_acquire_device: the acquisition search over the samples at device pointer
         samples_ptr; peaks (n_prn x 32 bytes), the optional grid and resolved shift go to device
@@ -1203,13 +1279,14 @@ class Device:
         return obs
 
     def run(self, scn, sink, first_block=0, n_blocks=-1, batch=100, threads=8, impair=None,
-            jam=None):
+            jam=None, echo=None):
         """Stream blocks [first_block, first_block + n_blocks) of Scenario scn through gss_run;
         sink(memoryview, first_block, nblocks) gets each batch's bytes in run order (the view
         is valid only during the call).  An exception in sink stops the run and is re-raised.
         impair: an Impair (additive noise, gss_run_opts_t.impair), None: off.  jam: an iterable of
         Jam (gss_run_opts_t.jam), None: none; jammers need an impair (its shift; sigma_q8 0: no
-        noise)."""
+        noise).  echo: an iterable of Echo (gss_run_opts_t.echo), None: none; echoes need an
+        impair as jammers do."""
         err = []
 
         def _sink(user, ptr, n, first, nb):
@@ -1222,11 +1299,12 @@ class Device:
 
         cb = SINK_FN(_sink)
         arr, nj = _jam_array(jam)
-        if impair is None and nj == 0:
+        earr, ne = _echo_array(echo)
+        if impair is None and nj == 0 and ne == 0:
             rc = lib().gss_run(self._h, scn._h, first_block, n_blocks, batch, threads, cb, None)
         else:
             ro = _RunOpts(None, None, None, None, C.pointer(impair) if impair is not None else None,
-                          arr, nj)
+                          arr, nj, earr, ne)
             rc = lib().gss_run_ex(self._h, scn._h, first_block, n_blocks, batch, threads, cb,
                                   None, C.byref(ro))
         if err:

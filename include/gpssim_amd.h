@@ -289,6 +289,77 @@ int gss_jam_host(const gss_impair_t *p, const gss_jam_t *jam, int n_jam, const i
 int gss_jam_device(gss_dev *d, const gss_impair_t *p, const gss_jam_t *jam, int n_jam,
                    const int16_t *iq, uint64_t sample0, size_t n, int fmt, void *out, void *stream);
 
+/* ---- multipath echoes ----------------------------------------------------------------------------
+   Up to GSS_MAXECHO specular echoes added to the 16-bit samples of a render, in place, before
+   the impairment or the jammers (an extension): each a delayed, attenuated, phase-shifted copy
+   of one satellite's signal (or of every satellite's), made from the channel rows the render
+   itself read.  Exact integers, one statement for host, device and oracle
+   (csrc/common/gss_echo.h).  Per block b and live pair (echo j, channel k < nch[b]; live: prn ==
+   0 or prn == ca_tbl + 1, with 0 <= ca_tbl < n_ca and 0 <= nav_tbl < n_nav and the row's doubles
+   in range, below), from the row:
+     P0 = carr0 >= 1.0 ? 0 : (uint64)(carr0 * 2^64)            (carr0 in [0, 1])
+     Ps = (uint64)(2 * (int64)trunc(carr_step * 2^63))
+     C0 = (int64)floor(code0 * 2^32),  Cs = (int64)floor(code_step * 2^32 + 0.5)
+     X0 = (((iword * 30 + ibit) * 20 + icode) * 1023) * 2^32 + C0 - delay        (int64)
+     g  = clamp((gain * alpha_q16 + 2^15) >> 16, -32767, 32767)   (int64 product, arithmetic)
+   and for sample s of the block, a = sample0 + b n + s its absolute index:
+     X    = X0 + s Cs,  q = X >> 32 (arithmetic)
+     chip = q mod 1023 (floored: 0..1022),  cp = max(q div 1023 (floored), 0)
+     bit  = cp div 20,  word = min(bit div 30, 59),  pos = bit mod 30
+     c    = bit (chip mod 32) of ca_bits[ca_tbl][chip div 32]        -> +-1
+     d    = (nav[nav_tbl][word] >> (29 - pos)) & 1                   -> +-1
+     Phi  = P0 + s Ps + theta0 + a dstep  (mod 2^64),  idx = Phi >> 55
+     E_I += d c cos512[idx] g,  E_Q += d c sin512[idx] g     (int32; |E| < 2^30 by the clamp on g)
+     y    = clamp_int16(x16 + ((E + 64) >> 7))                        for I and for Q
+   (tables of gss_lut).  With delay 0, alpha_q16 65536 and theta0 = dstep = 0 an echo is the
+   render's own term for that channel up to the Q32 rounding of the code step.  A delay that
+   reaches before the row's frame (iword = ibit = icode = 0 and code0 < delay: X < 0) takes the
+   periodic chip and the row's first data bit; that is a few microseconds per 30 s.  The index a
+   is absolute, as for the noise and the jammers, so the bytes do not depend on batches, block
+   ranges or ranks.
+   Ranges.  A row is live only with 0 <= carr0 <= 1, -1 < carr_step < 1, 0 <= code0 < 1023 and
+   0 <= code_step < 1024, where every conversion above is defined; any other row (a NaN or an
+   infinity among them) adds nothing, on the host and on the device alike.  X is an int64 in two's
+   complement: the chips counted from the frame's start, ((iword * 30 + ibit) * 20 + icode) * 1023
+   + code0 + n_per_blk * code_step, must stay below 2^31 (a frame holds 36,828,000 and a 0.1 s
+   block of the reference 102,300 more at any rate); beyond that X wraps and the chip and data
+   bit with it.  The calls cannot check this on device rows and do not on host rows.           */
+#define GSS_MAXECHO 4
+typedef struct gss_echo {
+    uint64_t delay;      /* code delay, 2^-32 chip; < 1023 * 2^32                              */
+    uint64_t theta0;     /* carrier phase offset at absolute sample 0, 2^-64 cycle             */
+    uint64_t dstep;      /* extra phase per sample (fading Doppler), 2^-64 cycle, mod 2^64     */
+    uint32_t alpha_q16;  /* amplitude ratio to the direct signal, 65536 = 1; <= 4 * 65536      */
+    int32_t  prn;        /* 1..32: rows with ca_tbl == prn - 1; 0: every channel               */
+} gss_echo_t;            /* 32 bytes */
+
+/* An echo from physical parameters, in IEEE double exactly as written here:
+     delay     = (uint64) floor(delay_m * 1023000 / 299792458 * 2^32 + 0.5)   in [0, 1023 * 2^32)
+     alpha_q16 = (uint32) floor(65536 * pow(10, -atten_db / 20) + 0.5)        <= 2^18
+     theta0    = (uint64) ((t - floor(t)) * 2^64),  t = phase_deg / 360   (a product of 2^64: 0)
+     dstep     = (uint64)(int64) floor(doppler_hz / fs_hz * 2^64 + 0.5)       |doppler_hz| < fs_hz / 2
+   prn 0..32 (0: every channel).  GSS_E_ARG for anything out of range or not finite.           */
+int gss_echo_make(double fs_hz, int prn, double delay_m, double atten_db, double phase_deg,
+                  double doppler_hz, gss_echo_t *out);
+/* The argument check of the calls below: GSS_E_ARG for n_echo outside 0..GSS_MAXECHO, a null
+   array with n_echo > 0, delay >= 1023 * 2^32, alpha_q16 > 2^18, prn outside 0..32.           */
+int gss_echo_check(const gss_echo_t *echo, int n_echo);
+/* The echoes added in place to iq: nblk * n_per_blk SC16 pairs, the render of the rows blk
+   [nblk][GSS_MAXCH], nch [nblk] with the tables ca_bits [n_ca][GSS_CA_WORDS] and nav [n_nav]
+   [GSS_NAV_WORDS]; sample0 is the absolute index of block 0's first sample.  n_echo = 0, and a
+   block with nch 0, leave the samples as they are.  GSS_E_ARG (nothing written) for invalid
+   echoes, nch outside 0..GSS_MAXCH, n_ca or n_nav < 1, or a range that passes 2^64.           */
+int gss_echo_host(const gss_echo_t *echo, int n_echo, const gss_chan_blk_t *blk,
+                  const int32_t *nch, int nblk, int n_per_blk, const uint32_t *ca_bits, int n_ca,
+                  const uint32_t *nav, int n_nav, uint64_t sample0, int16_t *iq);
+/* The same on the device: blk, nch, ca_bits, nav and iq are device pointers (nch is not read by
+   the host), echo is a host array read before the call returns; asynchronous on stream, no
+   allocation.  GSS_ECHO_PATH=plain (read per call) takes the plain kernel: one sample per
+   thread, straight from the definition and global memory.                                     */
+int gss_echo_device(gss_dev *d, const gss_echo_t *echo, int n_echo, const gss_chan_blk_t *blk,
+                    const int32_t *nch, int nblk, int n_per_blk, const uint32_t *ca_bits, int n_ca,
+                    const uint32_t *nav, int n_nav, uint64_t sample0, int16_t *iq, void *stream);
+
 /* ---- signal acquisition -------------------------------------------------------------------------
    A measurement of generated samples (an extension; the reference has no receiver): for every
    selected PRN a search over Doppler bins and code phases, the peak, and the noise floor around
@@ -617,6 +688,10 @@ typedef struct gss_cli {
        times (gss_jam_make at the run's rate); sets has_impair (sigma_q8 = 0 without noise)    */
     gss_jam_t jam[GSS_MAXJAM];
     int n_jam;
+    /* --multipath=<prn|all>,<delay_m>,<atten_db>[,<phase_deg>[,<doppler_hz>]], up to GSS_MAXECHO
+       times (gss_echo_make at the run's rate); sets has_impair (sigma_q8 = 0 without noise)   */
+    gss_echo_t echo[GSS_MAXECHO];
+    int n_echo;
 } gss_cli_t;
 int gss_cli_parse(int argc, char **argv, gss_cli_t *cli);
 void gss_cli_usage(void);
@@ -885,7 +960,7 @@ int gss_run(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int b
    the range (gss_carr_chain) and hands the end state to carr_out (if set) -- before the first
    batch renders.  Both callbacks return 0, or non-zero to abort the run (GSS_E_IO).
    opts == NULL: gss_run.  carr_in == NULL: blocks before first_block are planned and dropped
-   as in gss_run; impair and jam apply either way.                                            */
+   as in gss_run; impair, jam and echo apply either way.                                      */
 typedef struct gss_run_opts {
     int (*carr_in)(void *user, double *carr);             /* [GSS_MAXCH], out                  */
     int (*carr_out)(void *user, const double *carr);      /* [GSS_MAXCH]                       */
@@ -909,6 +984,11 @@ typedef struct gss_run_opts {
        shift; sigma_q8 = 0 for no noise); gss_jam_device then takes gss_impair_device's place. */
     const gss_jam_t *jam;
     int n_jam;
+    /* Optional (n_echo 0: none): multipath echoes, copied when the run starts.  They need impair
+       too; gss_echo_device runs on each slot's SC16 render and rows before the impairment or
+       the jammers.                                                                            */
+    const gss_echo_t *echo;
+    int n_echo;
 } gss_run_opts_t;
 int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int batch,
                int threads, gss_sink_fn sink, void *user, const gss_run_opts_t *opts);
