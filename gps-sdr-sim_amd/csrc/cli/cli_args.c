@@ -136,6 +136,35 @@ bad:
     return 1;
 }
 
+/* --bandwidth=<hz>[,<taps>] into c->fir: a low-pass of two-sided width <hz> with <taps> taps (63
+   by default) at the rate the run uses (a multiple of 10 Hz, gpssim.c:1877-1881), by
+   gss_fir_make. */
+static int fir_option(gss_cli_t *c, const char *val)
+{
+    char buf[128];
+    double bw = 0.0, taps = 63.0;
+    if (strlen(val) >= sizeof buf)
+        goto bad;
+    strcpy(buf, val);
+    char *comma = strchr(buf, ',');
+    if (comma) {
+        *comma = '\0';
+        if (parse_real(comma + 1, &taps) || taps < 3.0 || taps > 63.0 || taps != floor(taps))
+            goto bad;
+    }
+    if (parse_real(buf, &bw))
+        goto bad;
+    const double fs = floor(c->opt.samp_freq / 10.0) * 10.0;
+    if (gss_fir_make(fs, bw, (int)taps, &c->fir))
+        goto bad;
+    c->has_fir = 1;
+    return 0;
+bad:
+    fprintf(stderr, "ERROR: Invalid bandwidth (<hz>[,<taps>]: 0 < hz <= the sample rate, an odd "
+                    "number of taps in 3..63).\n");
+    return 1;
+}
+
 /* The noise options into c->impair.
      --cn0=<dB-Hz>        sigma = 250 sqrt(fs / (2 10^(cn0/10))) LSB per component: 250 is the carrier
                           table's amplitude, so this is the C/N0 of a satellite at gain 128 (path
@@ -148,8 +177,10 @@ bad:
                           2047 alpha_q16 / 65536 per echo (--multipath); 0 for -b 1, which keeps
                           only the sign
      --seed=<u64>         default 0
-   With --jam or --multipath and neither --cn0 nor --noise-sigma: sigma 0 (--noise-shift is then
-   accepted, --seed is not). */
+   With --jam, --multipath or --bandwidth and neither --cn0 nor --noise-sigma: sigma 0
+   (--noise-shift is then accepted, --seed is not).  --bandwidth leaves the automatic shift as it
+   is: the filter reads the shifted SC16 samples, which that shift fits into 16 bits, and its
+   DC gain is 1. */
 static int noise_options(gss_cli_t *c, const char *o_cn0, const char *o_sigma, const char *o_shift,
                          const char *o_seed)
 {
@@ -158,16 +189,16 @@ static int noise_options(gss_cli_t *c, const char *o_cn0, const char *o_sigma, c
         return 1;
     }
     if (!o_cn0 && !o_sigma) {
-        if (o_seed || (o_shift && c->n_jam == 0 && c->n_echo == 0)) {
+        if (o_seed || (o_shift && c->n_jam == 0 && c->n_echo == 0 && !c->has_fir)) {
             fprintf(stderr, "ERROR: --noise-shift and --seed need --cn0 or --noise-sigma.\n");
             return 1;
         }
-        if (c->n_jam == 0 && c->n_echo == 0)
+        if (c->n_jam == 0 && c->n_echo == 0 && !c->has_fir)
             return 0;
     }
     double v = 0.0, q8 = 0.0;
     if (!o_cn0 && !o_sigma) {
-        /* jammers or echoes alone: no noise */
+        /* jammers, echoes or the filter alone: no noise */
     } else if (o_cn0) {
         if (parse_real(o_cn0, &v) || v < -100.0 || v > 200.0) {
             fprintf(stderr, "ERROR: Invalid C/N0.\n");
@@ -246,7 +277,17 @@ int gss_cli_parse(int argc, char **argv, gss_cli_t *c)
     /* multipath echoes (--multipath=..., repeatable): the same */
     const char *o_echo[GSS_MAXECHO];
     int n_oecho = 0;
+    /* the front-end filter (--bandwidth=..., once) */
+    const char *o_fir = NULL;
     for (int i = 0; i < argc; i++) {
+        if (i > 0 && strncmp(argv[i], "--bandwidth=", 12) == 0) {
+            if (o_fir) {
+                fprintf(stderr, "ERROR: --bandwidth given twice.\n");
+                return 1;
+            }
+            o_fir = argv[i] + 12;
+            continue;
+        }
         if (i > 0 && strncmp(argv[i], "--multipath=", 12) == 0) {
             if (n_oecho == GSS_MAXECHO) {
                 fprintf(stderr, "ERROR: At most %d multipath echoes.\n", GSS_MAXECHO);
@@ -398,5 +439,7 @@ int gss_cli_parse(int argc, char **argv, gss_cli_t *c)
     for (int i = 0; i < n_oecho; i++)
         if (echo_option(c, o_echo[i]))
             return 1;
+    if (o_fir && fir_option(c, o_fir))
+        return 1;
     return noise_options(c, o_cn0, o_sigma, o_shift, o_seed);
 }

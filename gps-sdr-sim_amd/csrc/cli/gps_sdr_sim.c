@@ -332,7 +332,7 @@ static int run_rank(const gss_cli_t *cli, gss_scn *scn, const gss_scn_info_t *in
     gss_run_opts_t ro = {handoff ? handoff_in : NULL, handoff ? handoff_out : NULL, &h,
                          handoff && spec ? handoff_predict : NULL,
                          cli->has_impair ? &cli->impair : NULL, cli->jam, cli->n_jam,
-                         cli->echo, cli->n_echo};
+                         cli->echo, cli->n_echo, NULL};
     if (run_id && *run_id) {
         if (rank > 0)
             snprintf(h.in_path, sizeof h.in_path, "%s.gss-carr-%s-%lld", cli->out_file, run_id,
@@ -393,6 +393,17 @@ int main(int argc, char **argv)
         fprintf(stderr, "Echo %d: prn = %d, delay = %llu, alpha_q16 = %u, theta0 = %llu, dstep = %llu\n",
                 i, cli.echo[i].prn, (unsigned long long)cli.echo[i].delay, cli.echo[i].alpha_q16,
                 (unsigned long long)cli.echo[i].theta0, (unsigned long long)cli.echo[i].dstep);
+    if (cli.has_fir && rank == 0) {
+        double e2 = 0.0;
+        for (int k = 0; k < cli.fir.n_taps; k++)
+            e2 += (double)cli.fir.taps[k] * (double)cli.fir.taps[k];
+        fprintf(stderr, "Filter: taps = %d, delay = %d samples, noise gain = %.5f\n",
+                cli.fir.n_taps, (cli.fir.n_taps - 1) / 2, e2 / 268435456.0);
+    }
+    if (world > 1 && cli.has_fir) {        /* the ranks hand carriers over: no block before a range */
+        fprintf(stderr, "ERROR: --bandwidth is not supported with WORLD_SIZE > 1.\n");
+        return 1;
+    }
     if (world > 1)
         return run_rank(&cli, scn, &info, rank, world);
 
@@ -423,6 +434,7 @@ int main(int argc, char **argv)
     ro.n_jam = cli.n_jam;
     ro.echo = cli.echo;
     ro.n_echo = cli.n_echo;
+    ro.fir = cli.has_fir ? &cli.fir : NULL;
     if (gss_run_ex(dev, scn, 0, -1, batch, threads, write_sink, fp,
                    cli.has_impair ? &ro : NULL)) {
         fprintf(stderr, "\nERROR: %s\n", gss_last_error());

@@ -1,0 +1,303 @@
+/*
+ * gss_fir.hip — the front-end band-limit filter on the GPU (gss_fir_device,
+ * include/gpssim_amd.h): one gfx950 kernel per output format over the SC16 samples that the
+ * impairment or the jammers wrote, out of place.  It takes the outer shape of gss_impair.hip:
+ *
+ *   samples  a tile of 256 groups per workgroup and trip (a group: 4, 8 or 16 samples for SC16,
+ *            SC08, SC01: one 16-byte store, or one dword of bits); grid-stride over the tiles
+ *            under a cap of 2,048 workgroups
+ *   staging  the tile and the 64 samples before it go into LDS once, de-interleaved: one array
+ *            of 32-bit words per component, a word holding two consecutive samples.  The tile
+ *            itself by 16-byte loads; the 64 samples before it one per lane, from the input,
+ *            the halo (the first tile of a call alone) or zeros
+ *   thread   its window (32 words of history and its group's own, per component) is read from
+ *            LDS into registers once; every output is a chain of packed dot products
+ *            (__builtin_amdgcn_sdot2: v_dot2c_i32_i16) of window words and tap pairs
+ *   taps     paired on the host for both parities of an output's distance to a word
+ *            (gss_fir_pairs) and passed by value: every index into them is a constant of the
+ *            unrolled loop, which leaves at a wave-uniform test on n_taps
+ *   edges    the samples before the first 16-byte boundary of the input (and of the output's
+ *            store width) and after the last whole group go one by one (SC01: byte by byte)
+ *            through the definition, from global memory.  An input that is not 4-byte aligned,
+ *            or an input and output whose boundaries never coincide, has no whole group: the
+ *            call is then all edges, at the plain form's speed (18 to 46 times slower at the
+ *            headline window).  gss_run's buffers are aligned
+ *   plain    GSS_FIR_PATH=plain (read per call): every output that way (gss_fir_plain_kernel)
+ * The arithmetic is csrc/common/gss_fir.h, shared with the host statement gss_fir_host; sums of
+ * at most 32768 * 65535 are exact in int32 in any order.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include "gpssim_amd.h"
+#include "gss_dev.h"
+#include "../common/gss_fir.h"
+
+extern "C" int gss_fir_args(const gss_fir_t *fir, const void *in, const void *halo, size_t n,
+                            int fmt, const void *out);                         /* fir.c */
+
+namespace {
+
+constexpr int FIR_THREADS = 256;
+constexpr int FIR_GRID_MAX = 2048;
+constexpr int FIR_HIST = GSS_MAXTAP;            /* samples staged before a tile (>= T - 1)      */
+
+struct FirArgs {
+    const int16_t *in, *halo;
+    void *out;
+    uint64_t n;             /* samples                                                          */
+    uint64_t head;          /* samples before the first whole group (multiple of 4 for SC01)    */
+    uint64_t groups;        /* whole groups from `head` on                                      */
+    int32_t n_taps;
+    uint32_t even[GSS_FIR_NE], odd[GSS_FIR_NO];      /* gss_fir_pairs                           */
+};
+
+template <int FMT> struct FirFmt;
+template <> struct FirFmt<GSS_FMT_SC16> { static constexpr int NS = 4, ITEM = 1; };
+template <> struct FirFmt<GSS_FMT_SC08> { static constexpr int NS = 8, ITEM = 1; };
+template <> struct FirFmt<GSS_FMT_SC01> { static constexpr int NS = 16, ITEM = 4; };
+
+typedef short fir_s2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ int32_t fir_dot2(uint32_t x, uint32_t h, int32_t acc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(fir_s2, x), __builtin_bit_cast(fir_s2, h), acc,
+                                  false);
+#else
+    return acc + (int16_t)(x & 0xFFFFu) * (int16_t)(h & 0xFFFFu) +
+           (int16_t)(x >> 16) * (int16_t)(h >> 16);             /* the host pass only parses this */
+#endif
+}
+
+/* one output from the definition and global memory: v (rounded) of component c of sample j.  The
+   tap of index k is the low half of a pair; k is a constant in every copy of the body */
+__device__ __forceinline__ void fir_sample(const FirArgs &A, uint64_t j, int32_t *vi, int32_t *vq)
+{
+    int32_t ai = 0, aq = 0;
+#pragma unroll
+    for (int k = 0; k < GSS_MAXTAP; k++) {
+        if (k >= A.n_taps)
+            break;
+        const int32_t h = (int16_t)(((k & 1) ? A.odd[k / 2] : A.even[k / 2]) & 0xFFFFu);
+        const int64_t i = (int64_t)j - k;
+        ai += h * gss_fir_x(A.in, A.halo, A.n_taps, i, 0);
+        aq += h * gss_fir_x(A.in, A.halo, A.n_taps, i, 1);
+    }
+    *vi = gss_fir_round(ai);
+    *vq = gss_fir_round(aq);
+}
+
+/* one edge item: a sample (SC16, SC08) or the 4 samples of a byte (SC01) at index j */
+template <int FMT> __device__ __forceinline__ void fir_item(const FirArgs &A, uint64_t j)
+{
+    uint32_t byte = 0;
+#pragma unroll
+    for (int s = 0; s < FirFmt<FMT>::ITEM; s++) {
+        int32_t vi, vq;
+        fir_sample(A, j + s, &vi, &vq);
+        if constexpr (FMT == GSS_FMT_SC16) {
+            ((int16_t *)A.out)[2 * j] = (int16_t)gss_imp_sc16(vi);
+            ((int16_t *)A.out)[2 * j + 1] = (int16_t)gss_imp_sc16(vq);
+        } else if constexpr (FMT == GSS_FMT_SC08) {
+            ((int8_t *)A.out)[2 * j] = (int8_t)gss_imp_sc08(vi);
+            ((int8_t *)A.out)[2 * j + 1] = (int8_t)gss_imp_sc08(vq);
+        } else {
+            byte |= (vi > 0 ? 1u : 0u) << (7 - 2 * s) | (vq > 0 ? 1u : 0u) << (6 - 2 * s);
+        }
+    }
+    if constexpr (FMT == GSS_FMT_SC01)
+        ((uint8_t *)A.out)[j / 4] = (uint8_t)byte;
+}
+
+/* the group's 2 NS rounded values (I, Q interleaved) to A.out at sample j */
+template <int FMT>
+__device__ __forceinline__ void fir_store(const FirArgs &A, uint64_t j,
+                                          const int32_t (&v)[2 * FirFmt<FMT>::NS])
+{
+    constexpr int NS = FirFmt<FMT>::NS;
+    if constexpr (FMT == GSS_FMT_SC16) {
+        uint32_t o[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++)
+            o[s] = ((uint32_t)gss_imp_sc16(v[2 * s]) & 0xFFFFu) |
+                   ((uint32_t)gss_imp_sc16(v[2 * s + 1]) << 16);
+        *reinterpret_cast<uint4 *>((int16_t *)A.out + 2 * j) = make_uint4(o[0], o[1], o[2], o[3]);
+    } else if constexpr (FMT == GSS_FMT_SC08) {
+        uint32_t o[4];
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            o[d] = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                o[d] |= ((uint32_t)gss_imp_sc08(v[4 * d + b]) & 0xFFu) << (8 * b);
+        }
+        *reinterpret_cast<uint4 *>((int8_t *)A.out + 2 * j) = make_uint4(o[0], o[1], o[2], o[3]);
+    } else {
+        uint32_t o = 0;                                /* component i -> byte i / 8, bit 7 - i % 8 */
+#pragma unroll
+        for (int i = 0; i < 2 * NS; i++)
+            o |= (v[i] > 0 ? 1u : 0u) << (8 * (i / 8) + 7 - (i % 8));
+        *reinterpret_cast<uint32_t *>((uint8_t *)A.out + j / 4) = o;
+    }
+}
+
+template <int FMT>
+__global__ __launch_bounds__(FIR_THREADS) void gss_fir_kernel(FirArgs A)
+{
+    constexpr int NS = FirFmt<FMT>::NS, ITEM = FirFmt<FMT>::ITEM;
+    constexpr int TILE = FIR_THREADS * NS;               /* samples per workgroup and trip      */
+    constexpr int WORDS = (FIR_HIST + TILE) / 2;         /* per component                       */
+    constexpr int WIN = FIR_HIST / 2 + NS / 2;           /* a thread's window, words            */
+    __shared__ uint32_t S[2][WORDS];                     /* [component][(sample - first) / 2]   */
+    const int tid = threadIdx.x;
+    const uint64_t tiles = (A.groups + FIR_THREADS - 1) / FIR_THREADS;
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t base = A.head + t * TILE;         /* the tile's first sample             */
+        const uint64_t g = t * FIR_THREADS + tid;
+        __syncthreads();                                 /* the last trip's reads are done      */
+        if (tid < FIR_HIST) {                            /* sample base - 64 + tid              */
+            const int64_t i = (int64_t)base - FIR_HIST + tid;
+            int16_t *s16 = reinterpret_cast<int16_t *>(&S[0][0]);
+            s16[tid] = (int16_t)gss_fir_x(A.in, A.halo, A.n_taps, i, 0);
+            s16[2 * WORDS + tid] = (int16_t)gss_fir_x(A.in, A.halo, A.n_taps, i, 1);
+        }
+        if (g < A.groups) {
+            const uint4 *src =
+                reinterpret_cast<const uint4 *>(A.in + 2 * (base + (uint64_t)tid * NS));
+#pragma unroll
+            for (int u = 0; u < NS / 4; u++) {
+                const uint4 r = src[u];
+                const int w = FIR_HIST / 2 + tid * (NS / 2) + 2 * u;
+                S[0][w] = (r.x & 0xFFFFu) | (r.y << 16);
+                S[0][w + 1] = (r.z & 0xFFFFu) | (r.w << 16);
+                S[1][w] = (r.x >> 16) | (r.y & 0xFFFF0000u);
+                S[1][w + 1] = (r.z >> 16) | (r.w & 0xFFFF0000u);
+            }
+        }
+        __syncthreads();
+        if (g >= A.groups)
+            continue;
+        /* window word i holds samples n0 - 64 + 2 i and the next, n0 the group's first sample */
+        uint32_t W[2][WIN];
+#pragma unroll
+        for (int i = 0; i < WIN; i++) {
+            W[0][i] = S[0][tid * (NS / 2) + i];
+            W[1][i] = S[1][tid * (NS / 2) + i];
+        }
+        int32_t acc[2 * NS];
+#pragma unroll
+        for (int i = 0; i < 2 * NS; i++)
+            acc[i] = 0;
+        /* output r: even r reads word r / 2 + 32 - q with even[q], q = 0..T / 2 (taps 2 q and
+           2 q - 1); odd r reads word (r - 1) / 2 + 32 - q with odd[q], q = 0..(T - 1) / 2 (taps
+           2 q + 1 and 2 q) */
+#pragma unroll
+        for (int q = 0; q < GSS_FIR_NE; q++) {
+            if (2 * q > A.n_taps)
+                break;
+#pragma unroll
+            for (int r = 0; r < NS; r += 2) {
+                acc[2 * r] = fir_dot2(W[0][r / 2 + 32 - q], A.even[q], acc[2 * r]);
+                acc[2 * r + 1] = fir_dot2(W[1][r / 2 + 32 - q], A.even[q], acc[2 * r + 1]);
+            }
+            if (q == GSS_FIR_NO)
+                break;
+#pragma unroll
+            for (int r = 1; r < NS; r += 2) {
+                acc[2 * r] = fir_dot2(W[0][r / 2 + 32 - q], A.odd[q], acc[2 * r]);
+                acc[2 * r + 1] = fir_dot2(W[1][r / 2 + 32 - q], A.odd[q], acc[2 * r + 1]);
+            }
+        }
+        int32_t v[2 * NS];
+#pragma unroll
+        for (int i = 0; i < 2 * NS; i++)
+            v[i] = gss_fir_round(acc[i]);
+        fir_store<FMT>(A, base + (uint64_t)tid * NS, v);
+    }
+    /* the edges: [0, head) and [head + groups * NS, n) */
+    const uint64_t body = A.groups * NS, items = (A.n - body) / ITEM;
+    const uint64_t t0 = (uint64_t)blockIdx.x * FIR_THREADS + tid;
+    const uint64_t stride = (uint64_t)gridDim.x * FIR_THREADS;
+    for (uint64_t e = t0; e < items; e += stride) {
+        const uint64_t j = e * ITEM;
+        fir_item<FMT>(A, j < A.head ? j : j + body);
+    }
+}
+
+template <int FMT>
+__global__ __launch_bounds__(FIR_THREADS) void gss_fir_plain_kernel(FirArgs A)
+{
+    constexpr int ITEM = FirFmt<FMT>::ITEM;
+    const uint64_t t0 = (uint64_t)blockIdx.x * FIR_THREADS + threadIdx.x;
+    const uint64_t stride = (uint64_t)gridDim.x * FIR_THREADS;
+    for (uint64_t e = t0; e < A.n / ITEM; e += stride)
+        fir_item<FMT>(A, e * ITEM);
+}
+
+template <int FMT> void launch(const FirArgs &A, bool plain, unsigned grid, hipStream_t st)
+{
+    if (plain)
+        hipLaunchKernelGGL(gss_fir_plain_kernel<FMT>, dim3(grid), dim3(FIR_THREADS), 0, st, A);
+    else
+        hipLaunchKernelGGL(gss_fir_kernel<FMT>, dim3(grid), dim3(FIR_THREADS), 0, st, A);
+}
+
+}  // namespace
+
+extern "C" int gss_fir_device(gss_dev *d, const gss_fir_t *fir, const int16_t *in,
+                              const int16_t *halo, size_t n, int fmt, void *out, void *stream)
+{
+    if (!d)
+        return gss_fail(GSS_E_ARG, "invalid filter arguments");
+    const int rc = gss_fir_args(fir, in, halo, n, fmt, out);
+    if (rc || n == 0)
+        return rc;
+    const char *path = getenv("GSS_FIR_PATH");
+    const bool plain = path && strcmp(path, "plain") == 0;
+    if (path && *path && !plain)
+        return gss_fail(GSS_E_ARG, "GSS_FIR_PATH: '%s' (plain, or unset)", path);
+    if (hipSetDevice(d->ordinal) != hipSuccess)
+        return gss_fail(GSS_E_HIP, "hipSetDevice failed");
+    const size_t ns = fmt == GSS_FMT_SC16 ? 4 : fmt == GSS_FMT_SC08 ? 8 : 16;
+    const int item = fmt == GSS_FMT_SC01 ? 4 : 1;
+    FirArgs A;
+    memset(&A, 0, sizeof A);
+    A.in = in; A.halo = halo; A.out = out; A.n = n; A.n_taps = fir->n_taps;
+    gss_fir_pairs(fir, A.even, A.odd);
+    uint64_t grid;
+    if (plain) {
+        grid = (n / (uint64_t)item + FIR_THREADS - 1) / FIR_THREADS;
+    } else {
+        /* the least head after which the input is 16-byte aligned and the output aligned to its
+           store (16, 16, 4 bytes); none (pointers that never line up): every sample by the edges */
+        A.head = n;
+        A.groups = 0;
+        for (size_t h = 0; h < 16 && h <= n; h += (size_t)item) {
+            const uintptr_t ai = (uintptr_t)in + 4 * h;
+            const uintptr_t ao = (uintptr_t)out + (fmt == GSS_FMT_SC16   ? 4 * h
+                                                   : fmt == GSS_FMT_SC08 ? 2 * h
+                                                                         : h / 4);
+            if (ai % 16 == 0 && ao % (fmt == GSS_FMT_SC01 ? 4 : 16) == 0) {
+                A.head = h;
+                A.groups = (n - h) / ns;
+                break;
+            }
+        }
+        const uint64_t tiles = (A.groups + FIR_THREADS - 1) / FIR_THREADS;
+        const uint64_t items = (n - A.groups * ns) / (uint64_t)item;
+        const uint64_t eg = (items + FIR_THREADS - 1) / FIR_THREADS;
+        grid = tiles > eg ? tiles : eg;
+    }
+    grid = grid < 1 ? 1 : grid > FIR_GRID_MAX ? FIR_GRID_MAX : grid;
+    hipStream_t st = (hipStream_t)stream;
+    if (fmt == GSS_FMT_SC16)
+        launch<GSS_FMT_SC16>(A, plain, (unsigned)grid, st);
+    else if (fmt == GSS_FMT_SC08)
+        launch<GSS_FMT_SC08>(A, plain, (unsigned)grid, st);
+    else
+        launch<GSS_FMT_SC01>(A, plain, (unsigned)grid, st);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : gss_fail(GSS_E_HIP, "filter kernel: %s", hipGetErrorString(e));
+}

@@ -55,6 +55,8 @@
  *   GSS_RUN_RENDER_REST    set (unset)             M  with SPEC_CUS: the render stream on the others
  *   GSS_RUN_FORCE_EXACT    k (0)                   T  every k-th block of the run to the exact path
  *   GSS_RUN_LATE_VERDICTS  1 (0)                   T  the GPU proofs' rejects always redone in drain
+ *                                                     (not in a filtered run, opts->fir: it waits
+ *                                                     for each slot's proof and never redoes)
  *   GSS_RUN_TRACE          1 (0)                   M  timestamps on stderr; cached per process
  * Compile-time: GSS_RUN_NCOPY (1), GSS_RUN_DEPTH (2), GSS_RUN_AHEAD (2).
  */
@@ -77,6 +79,7 @@ extern "C" int gss_fail(int code, const char *fmt, ...);
 extern "C" void gss_pool_select(int id);             /* pool.c */
 extern "C" int gss_jam_check(const gss_jam_t *jam, int n_jam);   /* jam.c */
 extern "C" int gss_echo_check(const gss_echo_t *echo, int n_echo);   /* echo.c */
+extern "C" int gss_fir_check(const gss_fir_t *fir);                  /* fir.c */
 /* n bytes from src to dst by a copy kernel on st: pinned host or device memory on either side
    (gss_producers.hip; not exported) */
 int run_copy_launch(void *dst, const void *src, size_t n, hipStream_t st);
@@ -99,6 +102,10 @@ extern "C" __attribute__((weak)) int gss_echo_device(gss_dev *d, const gss_echo_
                                                      const uint32_t *ca_bits, int n_ca,
                                                      const uint32_t *nav, int n_nav,
                                                      uint64_t sample0, int16_t *iq, void *stream);
+/* ... and the front-end filter's (gss_fir.hip), which runs after them in a filtered run */
+extern "C" __attribute__((weak)) int gss_fir_device(gss_dev *d, const gss_fir_t *fir,
+                                                    const int16_t *in, const int16_t *halo,
+                                                    size_t n, int fmt, void *out, void *stream);
 
 #define RUN_TRY(x)                                                                           \
     do {                                                                                     \
@@ -381,7 +388,8 @@ struct Slot {
     uint8_t *d_out = nullptr, *h_out = nullptr;
     size_t h_out_bytes = 0, d_out_bytes = 0;   /* their sizes (pool_get / pool_put)        */
     uint8_t *d_imp = nullptr;        /* additive noise into SC08 / SC01: the impaired bytes (d_out
-                                        holds the SC16 render; SC16 is impaired in place)   */
+                                        holds the SC16 render; SC16 is impaired in place); in a
+                                        filtered run, any format: the filter's output       */
     size_t d_imp_bytes = 0;
     int32_t *d_status = nullptr, *h_status = nullptr;
     hipEvent_t rendered = nullptr;   /* compute stream: the slot's kernels are done      */
@@ -423,6 +431,13 @@ struct Run {
     gss_echo_t echo[GSS_MAXECHO];           /* the run's copy of opts->echo */
     int n_echo = 0;
     int fmt_out = 0;                 /* the scenario's format: what the sink receives          */
+    /* the front-end filter (opts->fir): the run's copy, and the last n_taps - 1 unfiltered SC16
+       samples before the next slot, kept on the device by the compute stream (two buffers taken
+       in turn: a slot shorter than the halo keeps part of the old one) */
+    gss_fir_t fir;
+    bool has_fir = false;
+    int16_t *d_halo[2] = {nullptr, nullptr};
+    int halo_cur = -1;               /* the buffer that holds the halo; -1: none yet (zeros)    */
     /* with opts->carr_in: the whole range planned up front (rows, carriers, checkpoints) */
     std::vector<gss_chan_blk_t> pre_blk;
     std::vector<int32_t> pre_nch;
@@ -1383,6 +1398,42 @@ int slot_in_reserve(Slot &sl, hipStream_t busy)
     return 0;
 }
 
+/* The filtered run's stages after the echoes: the impairment or the jammers write SC16 in place,
+   the filter writes the run's format into d_imp with the samples before the slot as its halo,
+   and the slot's last n_taps - 1 unfiltered samples become the next slot's halo.  Whole slots
+   in run order only: the filter's memory crosses every boundary */
+int filter_blocks(Run &r, Slot &sl, int b0, int nblk, hipStream_t st)
+{
+    if (b0 != 0 || nblk != sl.nb)
+        return gss_fail(GSS_E_STATE, "a filtered run renders whole slots only");
+    const size_t ns = (size_t)r.n_per_blk * (size_t)nblk;
+    int16_t *x = (int16_t *)sl.d_out;
+    const uint64_t s0 = (uint64_t)sl.first * (uint64_t)r.n_per_blk;
+    int rc = r.n_jam > 0 ? gss_jam_device(r.dev, r.impair, r.jam, r.n_jam, x, s0, ns, GSS_FMT_SC16,
+                                          x, st)
+                         : gss_impair_device(r.dev, r.impair, x, s0, ns, GSS_FMT_SC16, x, st);
+    if (rc)
+        return rc;
+    const size_t keep = (size_t)(r.fir.n_taps - 1);
+    const int16_t *halo = r.halo_cur >= 0 && keep > 0 ? r.d_halo[r.halo_cur] : nullptr;
+    rc = gss_fir_device(r.dev, &r.fir, x, halo, ns, r.fmt_out, sl.d_imp, st);
+    if (rc || keep == 0)
+        return rc;
+    const int nxt = r.halo_cur == 0 ? 1 : 0;
+    int16_t *h = r.d_halo[nxt];
+    if (ns >= keep) {
+        RUN_TRY(hipMemcpyAsync(h, x + 2 * (ns - keep), 4 * keep, hipMemcpyDeviceToDevice, st));
+    } else {
+        if (halo)
+            RUN_TRY(hipMemcpyAsync(h, halo + 2 * ns, 4 * (keep - ns), hipMemcpyDeviceToDevice, st));
+        else
+            RUN_TRY(hipMemsetAsync(h, 0, 4 * (keep - ns), st));
+        RUN_TRY(hipMemcpyAsync(h + 2 * (keep - ns), x, 4 * ns, hipMemcpyDeviceToDevice, st));
+    }
+    r.halo_cur = nxt;
+    return 0;
+}
+
 /* Additive noise: blocks [b0, b0 + nblk) of the slot, rendered at SC16 into d_out, through the
    impairment into the run's format on st (one launch: the blocks' samples are consecutive in the
    run, sample0 = run block * n_per_blk) */
@@ -1401,6 +1452,8 @@ int impair_blocks(Run &r, Slot &sl, int b0, int nblk, hipStream_t st)
         if (rc)
             return rc;
     }
+    if (r.has_fir)
+        return filter_blocks(r, sl, b0, nblk, st);
     if (r.n_jam > 0)
         return gss_jam_device(r.dev, r.impair, r.jam, r.n_jam, (const int16_t *)in, s0,
                               n * (size_t)nblk, r.fmt_out, out, st);
@@ -1491,13 +1544,16 @@ int submit_proven(Run &r, Slot &sl, hipStream_t cp)
     const hipStream_t st = r.st;
     const SlotDev v = slot_dev(sl);
     const int n_rows = sl.nav_first + sl.n_nav;
+    if (r.has_fir)                     /* a filtered run never defers the verdicts: no redo */
+        RUN_TRY(hipEventSynchronize(sl.proved));
     RUN_TRY(hipStreamWaitEvent(st, sl.proved, 0));
     /* the proof done (it ran ahead): its verdicts are on the host, and the blocks it rejected
        (rare) render on the exact path beside the certified ones, as with host proofs; else the
        verdicts come back with the bytes and drain redoes the rejected blocks */
     int nf = 0;
     sl.verdicts = 0;
-    const hipError_t q = r.m.late_verdicts ? hipErrorNotReady : hipEventQuery(sl.proved);
+    const hipError_t q = r.has_fir ? hipSuccess
+                         : r.m.late_verdicts ? hipErrorNotReady : hipEventQuery(sl.proved);
     if (q == hipSuccess) {
         nf = list_exact(sl);
         if (nf > 0) {
@@ -1591,6 +1647,8 @@ int redo_rejected(Run &r, Slot &sl)
     const int nf = list_exact(sl);
     if (nf == 0)
         return 0;
+    if (r.has_fir)
+        return gss_fail(GSS_E_STATE, "a filtered run cannot render blocks again");
     fill_lazy_ck(r, sl);
     const SlotDev v = slot_dev(sl);
     RUN_H2D(v.ck, sl.ck, sizeof(double) * GSS_MAXCH * GSS_NCK * (size_t)sl.nb, st);
@@ -1724,6 +1782,8 @@ int run_alloc(Run &r)
 {
     gss_ca_table(r.ca);
     hipError_t e = dev_alloc((void **)&r.d_ca, sizeof r.ca);
+    for (int i = 0; i < 2 && r.has_fir; i++)
+        THEN(e, dev_alloc((void **)&r.d_halo[i], 4 * (size_t)GSS_MAXTAP));
     THEN(e, r.m.render_rest ? cu_mask_stream(&r.st, r.m.spec_cus, true) : stream_get(&r.st, false));
     for (hipStream_t &c : r.cp)
         THEN(e, stream_get(&c, false));
@@ -1740,6 +1800,8 @@ void run_release_tables(Run &r)
 {
     dev_free(r.d_ca);
     dev_free(r.d_nav);
+    dev_free(r.d_halo[0]);
+    dev_free(r.d_halo[1]);
 }
 
 void run_release_streams(Run &r)
@@ -1762,7 +1824,7 @@ int slot_alloc(const Run &r, Slot &sl)
     THEN(e, pool_get((void **)&sl.h_out, r.bb * nb, true, r.ordinal, &sl.h_out_bytes));
     THEN(e, pin_alloc((void **)&sl.h_status, sizeof(int32_t)));
     THEN(e, pool_get((void **)&sl.d_out, r.bb_r * nb, false, r.ordinal, &sl.d_out_bytes));
-    if (r.impair && r.fmt != r.fmt_out)
+    if (r.impair && (r.fmt != r.fmt_out || r.has_fir))
         THEN(e, pool_get((void **)&sl.d_imp, r.bb * nb, false, r.ordinal, &sl.d_imp_bytes));
     THEN(e, dev_alloc((void **)&sl.d_status, sizeof(int32_t)));
     THEN(e, hipEventCreateWithFlags(&sl.done, ev));
@@ -1982,6 +2044,30 @@ void warm_walks(Run &r)
                                   (gss_spec_rec_t *)(w + 2 * WARM_IN + WARM_SPEC), r.spec_st);
 }
 
+/* the sink of a filtered range: the blocks before `first`, rendered for the filter's memory
+   alone, are kept from the caller's sink */
+struct TrimSink {
+    gss_sink_fn sink;
+    void *user;
+    int64_t first;
+    size_t bb;
+};
+
+int trim_sink(void *user, const void *bytes, size_t n, int64_t first_block, int nblocks)
+{
+    const TrimSink *t = (const TrimSink *)user;
+    int64_t skip = t->first - first_block;
+    skip = skip < 0 ? 0 : skip > nblocks ? nblocks : skip;
+    if (skip == nblocks)
+        return 0;
+    return t->sink(t->user, (const uint8_t *)bytes + t->bb * (size_t)skip, n - t->bb * (size_t)skip,
+                   first_block + skip, nblocks - (int)skip);
+}
+
+int run_range(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int batch, int threads,
+              gss_sink_fn sink, void *user, const gss_run_opts_t *opts, const gss_scn_info_t &info,
+              size_t bb, double t_enter);
+
 }  // namespace
 
 extern "C" int gss_run(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int batch,
@@ -2031,6 +2117,46 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
     if (n_echo > 0 && !gss_echo_device)
         return gss_fail(GSS_E_STATE, "echoes requested, but this build has no echo launch "
                                      "(gss_echo_device)");
+    const gss_fir_t *fir = opts ? opts->fir : nullptr;
+    if (fir && (!imp || opts->carr_in))
+        return gss_fail(GSS_E_ARG, "the filter needs an impairment (sigma_q8 = 0: none) and no "
+                                   "carrier hand-off (carr_in)");
+    if (fir && (rc = gss_fir_check(fir)) != 0)
+        return rc;
+    if (fir && !gss_fir_device)
+        return gss_fail(GSS_E_STATE, "a filter requested, but this build has no filter launch "
+                                     "(gss_fir_device)");
+    /* the filter's memory: a range that starts after block 0 also renders the blocks that hold
+       the n_taps - 1 samples before it (one block, unless a block is shorter than that) and a
+       wrapping sink keeps them from the caller's, so its bytes are the whole run's (an empty
+       range renders nothing more than it did) */
+    if (fir && first_block > 0 && fir->n_taps > 1 && n_blocks != 0) {
+        int64_t extra = ((int64_t)fir->n_taps - 2) / info.n_per_blk + 1;
+        extra = extra > first_block ? first_block : extra;
+        if (first_block - extra < info.next_block)
+            return gss_fail(GSS_E_STATE, "a filtered run from block %lld needs block %lld, but the "
+                            "scenario is at block %lld", (long long)first_block,
+                            (long long)(first_block - extra), (long long)info.next_block);
+        gss_run_opts_t inner = *opts;
+        const gss_fir_t taps = *fir;
+        inner.fir = &taps;
+        TrimSink trim = {sink, user, first_block, bb};
+        return run_range(d, s, first_block - extra, n_blocks < 0 ? n_blocks : n_blocks + extra,
+                         batch, threads, trim_sink, &trim, &inner, info, bb, t_enter);
+    }
+    return run_range(d, s, first_block, n_blocks, batch, threads, sink, user, opts, info, bb,
+                     t_enter);
+}
+
+namespace {
+
+int run_range(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int batch, int threads,
+              gss_sink_fn sink, void *user, const gss_run_opts_t *opts, const gss_scn_info_t &info,
+              size_t bb, double t_enter)
+{
+    const gss_impair_t *imp = opts ? opts->impair : nullptr;
+    const int n_jam = opts ? opts->n_jam : 0, n_echo = opts ? opts->n_echo : 0;
+    const gss_fir_t *fir = opts ? opts->fir : nullptr;
     const size_t bb_r = imp ? (size_t)info.n_per_blk * 4 : bb;
     if (batch <= 0)
         batch = 100;
@@ -2055,6 +2181,9 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
     r.n_echo = n_echo;
     for (int i = 0; i < n_echo; i++)
         r.echo[i] = opts->echo[i];
+    r.has_fir = fir != nullptr;
+    if (fir)
+        r.fir = *fir;
     r.fmt = imp ? GSS_FMT_SC16 : info.data_format;
     r.fmt_out = info.data_format;
     r.bb = bb;
@@ -2103,4 +2232,6 @@ extern "C" int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n
     tear_down(r);
     return err;
 }
+
+}  // namespace
 

@@ -182,6 +182,28 @@ class Echo(C.Structure):
                 f"alpha_q16={self.alpha_q16}, prn={self.prn})")
 
 
+MAXTAP = 64                                        # GSS_MAXTAP
+
+
+class Fir(C.Structure):
+    """gss_fir_t: the front-end filter's Q14 taps (include/gpssim_amd.h); fir_make() designs a
+    low-pass, Fir(taps=[...]) takes any taps."""
+    _fields_ = [("n_taps", C.c_int32), ("pad", C.c_int32), ("taps", C.c_int16 * MAXTAP)]
+
+    def __init__(self, taps=(), n_taps=None, pad=0):
+        taps = [int(t) for t in taps]
+        if len(taps) > MAXTAP:
+            raise ValueError(f"Fir: at most {MAXTAP} taps")
+        super().__init__(len(taps) if n_taps is None else int(n_taps), int(pad),
+                         (C.c_int16 * MAXTAP)(*taps))
+
+    def tap_list(self):
+        return [int(self.taps[k]) for k in range(max(0, min(self.n_taps, MAXTAP)))]
+
+    def __repr__(self):
+        return f"Fir(n_taps={self.n_taps}, pad={self.pad}, taps={self.tap_list()})"
+
+
 class Acq(C.Structure):
     """gss_acq_t: an acquisition search.  fs_hz, fmt (16 / 8 / 1), coh_ms x n_coh windows, bins
     -n_half..n_half of bin_hz (default 500 / coh_ms), qshift (-1: auto), prns (iterable of 1..32,
@@ -260,14 +282,16 @@ class _Cli(C.Structure):
     _fields_ = [("opt", _Opts), ("nav_file", C.c_char * 256), ("motion_file", C.c_char * 256),
                 ("out_file", C.c_char * 256), ("impair", Impair), ("has_impair", C.c_int),
                 ("jam", Jam * MAXJAM), ("n_jam", C.c_int),
-                ("echo", Echo * MAXECHO), ("n_echo", C.c_int)]
+                ("echo", Echo * MAXECHO), ("n_echo", C.c_int),
+                ("fir", Fir), ("has_fir", C.c_int)]
 
 
 class _RunOpts(C.Structure):                         # gss_run_opts_t
     _fields_ = [("carr_in", C.c_void_p), ("carr_out", C.c_void_p), ("carr_user", C.c_void_p),
                 ("carr_predict", C.c_void_p), ("impair", C.POINTER(Impair)),
                 ("jam", C.POINTER(Jam)), ("n_jam", C.c_int),
-                ("echo", C.POINTER(Echo)), ("n_echo", C.c_int)]
+                ("echo", C.POINTER(Echo)), ("n_echo", C.c_int),
+                ("fir", C.POINTER(Fir))]
 
 
 class _Info(C.Structure):
@@ -324,6 +348,10 @@ _SIGS = {
                                 _P, C.c_int, C.c_uint64, _P]),
     "gss_echo_device": (C.c_int, [_P, C.POINTER(Echo), C.c_int, _P, _P, C.c_int, C.c_int, _P,
                                   C.c_int, _P, C.c_int, C.c_uint64, _P, _P]),
+    "gss_fir_make": (C.c_int, [C.c_double, C.c_double, C.c_int, C.POINTER(Fir)]),
+    "gss_fir_check": (C.c_int, [C.POINTER(Fir)]),
+    "gss_fir_host": (C.c_int, [C.POINTER(Fir), _P, _P, C.c_size_t, C.c_int, _P]),
+    "gss_fir_device": (C.c_int, [_P, C.POINTER(Fir), _P, _P, C.c_size_t, C.c_int, _P, _P]),
     "gss_acq_sizes": (C.c_int, [C.POINTER(Acq), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32)]),
@@ -559,6 +587,36 @@ def echo_host(echo, blk, nch, ca, nav, n_per_blk, sample0, iq):
     _check(lib().gss_echo_host(arr, ne, _ptr(blk), _ptr(nch), nblk, int(n_per_blk), _ptr(ca),
                                ca.size // CA_WORDS, _ptr(nav), nav.size // NAV_WORDS,
                                int(sample0), _ptr(out)))
+    return out
+
+
+def fir_make(fs_hz, bw_hz, n_taps=63):
+    """A Fir from physical parameters (gss_fir_make): a Hamming-windowed sinc of two-sided width
+    bw_hz at the rate fs_hz with n_taps taps (odd, 3..63); DC gain 1, delay (n_taps - 1) / 2."""
+    f = Fir()
+    _check(lib().gss_fir_make(float(fs_hz), float(bw_hz), int(n_taps), C.byref(f)))
+    return f
+
+
+def fir_check(fir):
+    """gss_fir_check: raises GssError for a filter the calls refuse."""
+    _check(lib().gss_fir_check(C.byref(fir)))
+
+
+def fir_host(fir, iq, halo, fmt):
+    """The filter on the host (gss_fir_host): iq int16[2 n] SC16 samples, halo the n_taps - 1
+    samples before them (int16[2 (n_taps - 1)]) or None for zeros; returns the bytes of format
+    fmt as uint8."""
+    iq = np.ascontiguousarray(iq, np.int16).reshape(-1)
+    n = len(iq) // 2
+    if halo is not None:
+        halo = np.ascontiguousarray(halo, np.int16).reshape(-1)
+        if halo.size != 2 * max(fir.n_taps - 1, 0):
+            raise ValueError("fir_host: the halo is n_taps - 1 samples")
+        if halo.size == 0:
+            halo = None
+    out = np.zeros(impair_bytes(n, fmt) if fmt in (1, 8, 16) else 0, np.uint8)
+    _check(lib().gss_fir_host(C.byref(fir), _ptr(iq), _ptr(halo), n, int(fmt), _ptr(out)))
     return out
 
 
@@ -863,11 +921,14 @@ class Scenario:
             self.jam = [Jam.from_buffer_copy(cli.jam[i]) for i in range(cli.n_jam)]
         if cli.n_echo:                                 # --multipath (Device.run(echo=))
             self.echo = [Echo.from_buffer_copy(cli.echo[i]) for i in range(cli.n_echo)]
+        if cli.has_fir:                                # --bandwidth (Device.run(fir=))
+            self.fir = Fir.from_buffer_copy(cli.fir)
         return self, cli.out_file.decode()
 
     impair = None                # the command line's noise options (from_cli), else None
     jam = None                   # the command line's jammers (from_cli: a list of Jam), else None
     echo = None                  # the command line's echoes (from_cli: a list of Echo), else None
+    fir = None                   # the command line's front-end filter (from_cli: a Fir), else None
 
     def _init_info(self):
         inf = _Info()
@@ -1222,6 +1283,14 @@ class Device:
                                      C.c_void_p(nav_ptr), int(n_nav), int(sample0),
                                      C.c_void_p(iq_ptr), C.c_void_p(stream or None)))
 
+    def fir_device(self, fir, iq_ptr, halo_ptr, n, fmt, out_ptr, stream=0):
+        """gss_fir_device: the filter `fir` over n SC16 samples at device pointer iq_ptr, the
+        n_taps - 1 samples before them at halo_ptr (0: zeros), format fmt to out_ptr (out of
+        place); asynchronous on stream."""
+        _check(lib().gss_fir_device(self._h, C.byref(fir), C.c_void_p(iq_ptr),
+                                    C.c_void_p(halo_ptr or None), int(n), int(fmt),
+                                    C.c_void_p(out_ptr), C.c_void_p(stream or None)))
+
     def acquire(self, acq, samples_ptr, peaks_ptr, grid_ptr=0, qshift_ptr=0, stream=0):
         """gss_acquire_device: the acquisition search over the samples at device pointer
         samples_ptr; peaks (n_prn x 32 bytes), the optional grid and resolved shift go to device
@@ -1279,14 +1348,15 @@ class Device:
         return obs
 
     def run(self, scn, sink, first_block=0, n_blocks=-1, batch=100, threads=8, impair=None,
-            jam=None, echo=None):
+            jam=None, echo=None, fir=None):
         """Stream blocks [first_block, first_block + n_blocks) of Scenario scn through gss_run;
         sink(memoryview, first_block, nblocks) gets each batch's bytes in run order (the view
         is valid only during the call).  An exception in sink stops the run and is re-raised.
         impair: an Impair (additive noise, gss_run_opts_t.impair), None: off.  jam: an iterable of
         Jam (gss_run_opts_t.jam), None: none; jammers need an impair (its shift; sigma_q8 0: no
         noise).  echo: an iterable of Echo (gss_run_opts_t.echo), None: none; echoes need an
-        impair as jammers do."""
+        impair as jammers do.  fir: a Fir (gss_run_opts_t.fir), the front-end filter before the
+        quantiser, None: none; it needs an impair too."""
         err = []
 
         def _sink(user, ptr, n, first, nb):
@@ -1300,11 +1370,11 @@ class Device:
         cb = SINK_FN(_sink)
         arr, nj = _jam_array(jam)
         earr, ne = _echo_array(echo)
-        if impair is None and nj == 0 and ne == 0:
+        if impair is None and nj == 0 and ne == 0 and fir is None:
             rc = lib().gss_run(self._h, scn._h, first_block, n_blocks, batch, threads, cb, None)
         else:
             ro = _RunOpts(None, None, None, None, C.pointer(impair) if impair is not None else None,
-                          arr, nj, earr, ne)
+                          arr, nj, earr, ne, C.pointer(fir) if fir is not None else None)
             rc = lib().gss_run_ex(self._h, scn._h, first_block, n_blocks, batch, threads, cb,
                                   None, C.byref(ro))
         if err:

@@ -357,6 +357,9 @@ def run_node(argv, rank, world, local, backend="nccl", chunk_blocks=None, thread
     from .shard import Baton, device_walker, plan_window
 
     scn, out_file = Scenario.from_cli(argv)
+    if scn.fir is not None:
+        raise ValueError("run_node: the front-end filter (--bandwidth) is not supported in the "
+                         "whole-node run; use gps-sdr-sim")
     if scn.echo is not None:
         raise ValueError("run_node: multipath echoes (--multipath) are not supported in the "
                          "whole-node run; use gps-sdr-sim")

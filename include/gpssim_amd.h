@@ -360,6 +360,57 @@ int gss_echo_device(gss_dev *d, const gss_echo_t *echo, int n_echo, const gss_ch
                     const int32_t *nch, int nblk, int n_per_blk, const uint32_t *ca_bits, int n_ca,
                     const uint32_t *nav, int n_nav, uint64_t sample0, int16_t *iq, void *stream);
 
+/* ---- front-end band-limit filter ----------------------------------------------------------------
+   A causal FIR filter with real taps over the 16-bit samples that the impairment or the jammers
+   wrote (an extension: the IF filter in front of a receiver's ADC), applied before the
+   quantiser.  Exact integers, one statement for host, device and oracle (csrc/common/gss_fir.h).
+   The taps are Q14 (16384: a gain of 1).  For each component c (I or Q) of the SC16 input x and
+   T = n_taps:
+     acc[n] = sum_{k=0}^{T-1} taps[k] * x_c[n - k]          (int32)
+     v      = (acc + 2^13) >> 14                             (arithmetic shift)
+   and the output stage is the impairment's with w = v: SC16 clamp(v, -32768, 32767), SC08
+   clamp(v >> 4, -128, 127), SC01 v > 0 in the reference's bit order.  x[n - k] for an index before
+   the call's first sample comes from a halo, the T - 1 samples that precede in[0] (halo[T - 2] is
+   x[-1]); a null halo stands for zeros, so a run's samples before absolute index 0 are zero.
+   sum |taps[k]| <= 65535 makes |acc| <= 32768 * 65535 < 2^31: every sum is exact in int32 in any
+   order, so packed 16-bit dot products agree bit for bit.                                      */
+#define GSS_MAXTAP 64
+typedef struct gss_fir {
+    int32_t n_taps;            /* T: 1..GSS_MAXTAP                                              */
+    int32_t pad;               /* 0                                                             */
+    int16_t taps[GSS_MAXTAP];  /* Q14; taps[k] for k >= n_taps are not read                     */
+} gss_fir_t;                   /* 136 bytes */
+
+/* A Hamming-windowed sinc of two-sided width bw_hz at the rate fs_hz, in IEEE double exactly as
+   written here:
+     M = n_taps - 1,  c = bw_hz / fs_hz
+     for k = 0..M:   m = k - M/2
+                     s = (m == 0) ? c : sin(pi * c * m) / (pi * m)
+                     d[k] = s * (0.54 - 0.46 * cos(2 * pi * k / M))
+     S = d[0] + d[1] + ... (in index order)
+     taps[k] = (int16) floor(d[k] / S * 16384 + 0.5);   taps[M/2] += 16384 - sum(taps)
+   so the DC gain is exactly 1, the taps are symmetric and the group delay is M/2 samples.
+   GSS_E_ARG for n_taps even or outside 3..63, bw_hz <= 0, bw_hz > fs_hz, or a non-finite
+   argument.  bw_hz == fs_hz: a single tap of 16384 at the centre (a pure delay of M/2).       */
+int gss_fir_make(double fs_hz, double bw_hz, int n_taps, gss_fir_t *out);
+/* The argument check of the calls below: GSS_E_ARG for a null filter, n_taps outside
+   1..GSS_MAXTAP, pad != 0, or sum |taps[k]| > 65535 over k < n_taps.                          */
+int gss_fir_check(const gss_fir_t *fir);
+/* The filter over n SC16 samples in (I, Q int16 pairs; 2-byte aligned) into format fmt at out:
+   4 n, 2 n or n / 4 bytes (SC01: n a multiple of 4).  halo: the n_taps - 1 SC16 samples before
+   in[0], or null for zeros.  Out of place: GSS_E_ARG (nothing written) when in and out overlap,
+   and for an invalid filter, format or pointer.  Any n is accepted, n < n_taps - 1 too.       */
+int gss_fir_host(const gss_fir_t *fir, const int16_t *in, const int16_t *halo, size_t n, int fmt,
+                 void *out);
+/* The same on the device: in, halo and out are device pointers, fir is a host struct read before
+   the call returns; asynchronous on stream, no allocation.  GSS_FIR_PATH=plain (read per call)
+   takes the plain kernel: one output per thread, straight from the definition and global
+   memory.  The staged kernel needs in 4-byte aligned and some sample h < 16 at which in + 4 h and
+   the output's byte of sample h are both 16-byte aligned (SC01: 4-byte); other pointers are
+   accepted and give the same bytes at the plain kernel's speed.                                */
+int gss_fir_device(gss_dev *d, const gss_fir_t *fir, const int16_t *in, const int16_t *halo,
+                   size_t n, int fmt, void *out, void *stream);
+
 /* ---- signal acquisition -------------------------------------------------------------------------
    A measurement of generated samples (an extension; the reference has no receiver): for every
    selected PRN a search over Doppler bins and code phases, the peak, and the noise floor around
@@ -692,6 +743,10 @@ typedef struct gss_cli {
        times (gss_echo_make at the run's rate); sets has_impair (sigma_q8 = 0 without noise)   */
     gss_echo_t echo[GSS_MAXECHO];
     int n_echo;
+    /* --bandwidth=<hz>[,<taps>] (63 taps by default), once: gss_fir_make at the run's rate; sets
+       has_impair (sigma_q8 = 0 without noise)                                                 */
+    gss_fir_t fir;
+    int has_fir;
 } gss_cli_t;
 int gss_cli_parse(int argc, char **argv, gss_cli_t *cli);
 void gss_cli_usage(void);
@@ -960,7 +1015,7 @@ int gss_run(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int b
    the range (gss_carr_chain) and hands the end state to carr_out (if set) -- before the first
    batch renders.  Both callbacks return 0, or non-zero to abort the run (GSS_E_IO).
    opts == NULL: gss_run.  carr_in == NULL: blocks before first_block are planned and dropped
-   as in gss_run; impair, jam and echo apply either way.                                      */
+   as in gss_run; impair, jam and echo apply either way (fir needs carr_in == NULL).          */
 typedef struct gss_run_opts {
     int (*carr_in)(void *user, double *carr);             /* [GSS_MAXCH], out                  */
     int (*carr_out)(void *user, const double *carr);      /* [GSS_MAXCH]                       */
@@ -989,6 +1044,15 @@ typedef struct gss_run_opts {
        the jammers.                                                                            */
     const gss_echo_t *echo;
     int n_echo;
+    /* Optional (null: none): the front-end filter, copied when the run starts.  It needs impair
+       too (sigma_q8 = 0: the plain chain) and no carr_in.  The impairment or the jammers then
+       write SC16 in place and gss_fir_device writes the run's format; the run keeps the last
+       n_taps - 1 unfiltered samples of each slot on the device as the next slot's halo, and with
+       first_block > 0 it also renders the blocks that hold the n_taps - 1 samples before the
+       range (one block) and keeps them from the sink, so the bytes do not depend on batches or
+       on where a range starts.  The scenario must not have passed those blocks (GSS_E_STATE).
+       A filtered run waits for a slot's GPU proof before it renders the slot.                 */
+    const gss_fir_t *fir;
 } gss_run_opts_t;
 int gss_run_ex(gss_dev *d, gss_scn *s, int64_t first_block, int64_t n_blocks, int batch,
                int threads, gss_sink_fn sink, void *user, const gss_run_opts_t *opts);

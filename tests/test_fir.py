@@ -1,0 +1,458 @@
+"""The front-end band-limit filter (include/gpssim_amd.h, gss_fir_t), the parts that need no GPU:
+the host statement gss_fir_host against the restatement of tests/fir_oracle.py byte for byte,
+ranges that compose through the halo, gss_fir_make against its formula and its stated response,
+the noise gain, what the receiver sees of an out-of-band jammer, the command-line option, and
+gss_run with the filter on the CPU fakes of tests/helpers (fir_fake.cpp)."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import NAV, REPO
+
+import gpssim_amd as G
+import acq_oracle as AO
+import fir_oracle as O
+
+NS = (1, 2, 3, 7, 33, 62, 63, 64, 1023, 1025, 4099)
+TS = (1, 2, 3, 31, 63, 64)
+
+
+def sizes(fmt):
+    """the list of n; SC01 takes multiples of 4 samples, as gss_impair_host does"""
+    return NS if fmt != 1 else tuple(sorted({(n + 3) // 4 * 4 for n in NS}))
+
+
+def samples(rng, n):
+    return rng.integers(-32768, 32768, 2 * n).astype(np.int16)
+
+
+# ---- gss_fir_host against the oracle -----------------------------------------------------------
+@pytest.mark.parametrize("T", TS)
+@pytest.mark.parametrize("fmt", [16, 8, 1])
+def test_fir_host_equals_oracle(fmt, T):
+    rng = np.random.default_rng(100 * fmt + T)
+    for n in sizes(fmt):
+        taps = O.random_taps(rng, T)
+        x = samples(rng, n)
+        halo = samples(rng, T - 1)
+        f = G.Fir(taps)
+        for h in (None, halo):
+            got = G.fir_host(f, x, h, fmt)
+            assert np.array_equal(got, O.fir(taps, x, h, fmt)), (n, h is None)
+
+
+@pytest.mark.parametrize("T", TS)
+@pytest.mark.parametrize("fmt", [16, 8, 1])
+def test_fir_host_at_the_ends_of_int32(fmt, T):
+    """sum |h| = 65535 against -32768 everywhere (taps of one sign: both ends of int32) and
+    against 32767 with the signs of the taps; the SC16 and SC08 clamps fire"""
+    n = 68
+    low = np.full(2 * n, -32768, np.int16)
+    for sign in (1, -1):
+        taps = O.extreme_taps(T, sign)
+        halo = np.full(2 * (T - 1), -32768, np.int16)
+        v = O.values(taps, low, halo)
+        if T > 2:                                             # acc at an end of int32
+            assert int(v[0]) == (-sign * 32768 * 65535 + 8192) >> 14
+        assert np.array_equal(G.fir_host(G.Fir(taps), low, halo, fmt), O.fir(taps, low, halo, fmt))
+        assert np.array_equal(G.fir_host(G.Fir(taps), low, None, fmt), O.fir(taps, low, None, fmt))
+    taps = O.extreme_taps(T, 0)
+    x = O.sign_matched(taps, n, 65)
+    v = O.values(taps, x, None).reshape(-1, 2)
+    if T > 2:
+        assert int(v[65, 0]) == (32767 * 65535 + 8192) >> 14
+    got = G.fir_host(G.Fir(taps), x, None, fmt)
+    assert np.array_equal(got, O.fir(taps, x, None, fmt))
+    if fmt == 16 and T > 2:
+        assert got.view(np.int16).reshape(-1, 2)[65, 0] == 32767        # the clamp
+    x = O.sign_matched(taps, n, 65, -32767)
+    assert np.array_equal(G.fir_host(G.Fir(taps), x, None, fmt), O.fir(taps, x, None, fmt))
+
+
+@pytest.mark.parametrize("fmt", [16, 8, 1])
+def test_ranges_compose_through_the_halo(fmt):
+    """a range split at every position in 1..T+1 and at n-1 (SC01: the multiples of 4 among them
+    and n-4), the second part given the first part's last T-1 inputs as halo, equals one call"""
+    rng = np.random.default_rng(5)
+    n = 200
+    per = {16: 4, 8: 2, 1: 0.25}[fmt]
+    for T in TS:
+        taps = O.random_taps(rng, T)
+        f = G.Fir(taps)
+        x = samples(rng, n)
+        halo0 = samples(rng, T - 1)
+        whole = G.fir_host(f, x, halo0, fmt)
+        cuts = list(range(1, T + 2)) + [n - 1]
+        if fmt == 1:
+            cuts = sorted({c for c in cuts if c % 4 == 0} | {n - 4})
+        for cut in cuts:
+            ext = np.concatenate([halo0, x[:2 * cut]])
+            halo1 = ext[len(ext) - 2 * (T - 1):] if T > 1 else None
+            a = G.fir_host(f, x[:2 * cut], halo0, fmt)
+            b = G.fir_host(f, x[2 * cut:], halo1, fmt)
+            assert len(a) == int(cut * per)
+            assert np.array_equal(np.concatenate([a, b]), whole), (T, cut)
+
+
+@pytest.mark.parametrize("fmt", [16, 8, 1])
+def test_single_tap_is_a_delay(fmt):
+    rng = np.random.default_rng(6)
+    n = 128
+    x = samples(rng, n)
+    zero = G.impair_host(G.Impair(0, 0, 0), x, 0, fmt)
+    taps = [16384]
+    assert np.array_equal(G.fir_host(G.Fir(taps), x, None, fmt), zero)
+    for d in (1, 5, 31, 63):
+        taps = [0] * d + [16384]
+        delayed = np.concatenate([np.zeros(2 * d, np.int16), x[:2 * (n - d)]])
+        want = G.impair_host(G.Impair(0, 0, 0), delayed, 0, fmt)
+        assert np.array_equal(G.fir_host(G.Fir(taps), x, None, fmt), want), d
+
+
+BAD_FIRS = [dict(taps=[1], n_taps=0), dict(taps=[1], n_taps=65), dict(taps=[1], n_taps=-1),
+            dict(taps=[1, 2], pad=1), dict(taps=[32767, 32767, 2]),
+            dict(taps=[-32768, -32768]), dict(taps=[1024] * 64)]
+
+
+def test_fir_check_refusals_and_overlap():
+    x = np.arange(64, dtype=np.int16)
+    out = np.full(128, 0x5A, np.uint8)
+    f = G.lib().gss_fir_host
+    P = lambda a, off=0: C.c_void_p(a.ctypes.data + off)
+    good = G.Fir([32767, -32767, 1])
+    assert O.check(3, 0, [32767, -32767, 1])
+    G.fir_check(good)
+    assert f(C.byref(good), P(x), None, 32, 16, P(out)) == 0 and not (out == 0x5A).all()
+    out[:] = 0x5A
+    for bad in BAD_FIRS:
+        b = G.Fir(**bad)
+        assert not O.check(b.n_taps, b.pad, list(b.taps)), bad
+        assert G.lib().gss_fir_check(C.byref(b)) == -1, bad
+        assert f(C.byref(b), P(x), None, 32, 16, P(out)) == -1, bad
+        with pytest.raises(G.GssError):
+            G.fir_check(b)
+    assert G.lib().gss_fir_check(None) == -1
+    assert f(None, P(x), None, 32, 16, P(out)) == -1
+    assert f(C.byref(good), P(x), None, 32, 4, P(out)) == -1              # format
+    assert f(C.byref(good), P(x), None, 30, 1, P(out)) == -1              # SC01: n % 4
+    assert f(C.byref(good), None, None, 32, 16, P(out)) == -1
+    assert f(C.byref(good), P(x), None, 32, 16, None) == -1
+    assert f(C.byref(good), P(x, 1), None, 16, 16, P(out)) == -1          # odd input address
+    assert f(C.byref(good), P(x), None, 16, 16, P(out, 1)) == -1          # odd SC16 output
+    assert (out == 0x5A).all()
+    assert f(C.byref(good), P(x), None, 0, 16, None) == 0                 # nothing to do
+    # overlapping buffers: in place, and either end of the output inside the input
+    buf = np.arange(256, dtype=np.int16)
+    keep = buf.copy()
+    for off_in, off_out, n, fmt in ((0, 0, 32, 16), (0, 4 * 31, 32, 16), (64, 0, 32, 16),
+                                    (0, 0, 32, 8), (0, 127, 32, 8), (0, 127, 32, 1),
+                                    (4, 0, 32, 1)):
+        assert f(C.byref(good), P(buf, off_in), None, n, fmt, P(buf, off_out)) == -1
+    assert f(C.byref(good), P(buf, 0), None, 32, 16, P(buf, 128)) == 0    # adjacent: accepted
+    assert np.array_equal(buf[:64], keep[:64])
+    with pytest.raises(ValueError):
+        G.fir_host(good, x, x[:2], 16)                                    # a halo of the wrong size
+
+
+# ---- gss_fir_make ------------------------------------------------------------------------------
+TABLE = [  # fs, bw, taps, noise gain
+    (1e6, 700e3, 63, 0.68928), (1e6, 500e3, 63, 0.48819), (2.6e6, 2.0e6, 63, 0.75772),
+    (2.6e6, 2.0e6, 31, 0.74613), (20e6, 2.046e6, 63, 0.08955)]
+
+
+@pytest.mark.parametrize("fs,bw,T,gain", TABLE)
+def test_fir_make_table(fs, bw, T, gain):
+    f = G.fir_make(fs, bw, T)
+    taps = f.tap_list()
+    assert f.n_taps == T and f.pad == 0 and len(taps) == T
+    assert taps == taps[::-1] and sum(taps) == 16384
+    assert sum(abs(t) for t in taps) <= 36156
+    assert all(int(f.taps[k]) == 0 for k in range(T, G.MAXTAP))
+    want = O.make(fs, bw, T)
+    assert max(abs(a - b) for a, b in zip(taps, want)) <= 1
+    assert abs(O.noise_gain(taps) - gain) < 2e-4
+    # the response: pass and stop at least 3.3 fs / (2 T) inside or outside bw / 2
+    edge, tw = bw / 2 / fs, 3.3 / (2 * T)
+    grid = np.linspace(0, 0.5, 2001)
+    H = O.response_db(taps, grid)
+    pb, sb = H[grid <= edge - tw], H[grid >= edge + tw]
+    print("pass %.3f .. %.3f dB, stop %.1f dB, edge %.3f dB" %
+          (pb.min(), pb.max(), sb.max() if len(sb) else float("nan"), O.response_db(taps, edge)[0]))
+    assert len(pb) > 0 and pb.min() >= -0.1 and pb.max() <= 0.1
+    assert len(sb) > 0 and sb.max() <= -40.0
+    assert abs(O.response_db(taps, edge)[0] + 6.0) <= 0.1
+
+
+def test_fir_make_forms_and_rejections():
+    for T in (3, 5, 15, 63):
+        for c in (0.01, 0.3, 0.999, 1.0):
+            f = G.fir_make(1e6, c * 1e6, T)
+            taps = f.tap_list()
+            assert taps == taps[::-1] and sum(taps) == 16384 and sum(map(abs, taps)) <= 65535
+            assert max(abs(a - b) for a, b in zip(taps, O.make(1e6, c * 1e6, T))) <= 1
+    f = G.fir_make(2.6e6, 2.6e6, 31)                      # bw == fs: a pure delay of M / 2
+    assert f.tap_list() == [0] * 15 + [16384] + [0] * 15
+    assert G.fir_make(1e6, 5e5).n_taps == 63
+    nan, inf = float("nan"), float("inf")
+    for args in ((1e6, 5e5, 2), (1e6, 5e5, 62), (1e6, 5e5, 1), (1e6, 5e5, 65), (1e6, 5e5, 64),
+                 (1e6, 0.0, 63), (1e6, -1.0, 63), (1e6, 1e6 + 1, 63), (nan, 5e5, 63),
+                 (1e6, nan, 63), (inf, 5e5, 63), (1e6, inf, 63), (0.0, 0.0, 63), (-1e6, 5e5, 63)):
+        with pytest.raises(G.GssError) as e:
+            G.fir_make(*args)
+        assert e.value.code == -1, args
+    out = G.Fir([7, 7, 7])
+    assert G.lib().gss_fir_make(1e6, 5e5, 4, C.byref(out)) == -1 and out.tap_list() == [7, 7, 7]
+    assert G.lib().gss_fir_make(1e6, 5e5, 5, None) == -1
+
+
+# ---- the noise ---------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def noise():
+    z = np.zeros(2 << 20, np.int16)
+    return {seed: G.impair_host(G.Impair(256 * 1000, 0, seed), z, 0, 16).view(np.int16)
+            for seed in (7, 8, 9)}
+
+
+@pytest.mark.parametrize("fs,bw,T", [(1e6, 700e3, 63), (2.6e6, 2.0e6, 31), (20e6, 2.046e6, 63)])
+def test_noise_gain(noise, fs, bw, T):
+    """white noise of sigma 1000 LSB through the taps: the variance ratio is sum h^2 / 2^28 within
+    1 % (the prototype: at most 0.23 %)"""
+    f = G.fir_make(fs, bw, T)
+    want = O.noise_gain(f.tap_list())
+    for seed, x in noise.items():
+        y = G.fir_host(f, x, None, 16).view(np.int16)
+        ratio = float(np.var(y[2 * T:].astype(np.float64)) / np.var(x.astype(np.float64)))
+        print("seed %d: ratio %.5f against %.5f (%.2f %%)" % (seed, ratio, want,
+                                                            100 * (ratio / want - 1)))
+        assert abs(ratio / want - 1) <= 0.01
+
+
+# ---- what the receiver sees --------------------------------------------------------------------
+PHYS_SIGMA = int(np.floor(256 * 250 * np.sqrt(AO.PHYS_FS / (2 * 10 ** (AO.PHYS_CN0 / 10))) + 0.5))
+SHIFT = {16: 0, 8: 2}
+
+
+def jammed(fmt, f_hz):
+    clean, blk, nch = AO.noisy_block(16, clean=True)
+    j = G.jam_make(float(AO.PHYS_FS), 30.0, f_hz)
+    mid = G.jam_host(G.Impair(PHYS_SIGMA, SHIFT[fmt], 7), [j], clean.view(np.int16), 0, 16)
+    return mid.view(np.int16), blk, nch
+
+
+def nothing_found(peaks):
+    ratios = [G.acq_ratio(p) for p in peaks]
+    print("largest ratio %.2f against %.2f" % (max(ratios), AO.phys_threshold()))
+    assert len(ratios) == 32 and max(ratios) < AO.phys_threshold()
+
+
+def found_delayed(peaks, blk, nch, delay):
+    """AO.check_physical on the peaks with the filter's group delay taken off their code phase"""
+    p = peaks.copy()
+    p["tau"] = (p["tau"] - delay) % 1000
+    AO.check_physical(p, blk, nch, level=False, found=True)
+    ratios = {int(q["prn"]): G.acq_ratio(q) for q in peaks}
+    print("smallest present %.2f, largest absent %.2f" % (
+        min(r for k, r in ratios.items() if k not in AO.ABSENT and r >= AO.phys_threshold()),
+        max(ratios[a] for a in AO.ABSENT)))
+
+
+@pytest.mark.parametrize("fmt", [16, 8])
+def test_receiver_without_the_filter(fmt):
+    """a tone 30 dB above a satellite, 450 kHz off the carrier: nothing reaches the threshold"""
+    mid, _, _ = jammed(fmt, 450e3)
+    data = G.fir_host(G.Fir([16384]), mid, None, fmt)            # the quantiser alone
+    assert np.array_equal(data, G.impair_host(G.Impair(0, 0, 0), mid, 0, fmt))
+    peaks, _, _ = G.acquire_host(AO.PHYS_ACQ(fmt), data)
+    nothing_found(peaks)
+
+
+@pytest.mark.parametrize("fmt", [16, 8])
+def test_receiver_behind_the_filter(fmt):
+    """the 700 kHz filter takes the tone out: all eleven satellites within one bin and one sample
+    of tau + 31 and over the threshold, the absent PRNs under it"""
+    mid, blk, nch = jammed(fmt, 450e3)
+    f = G.fir_make(float(AO.PHYS_FS), 700e3, 63)
+    peaks, _, _ = G.acquire_host(AO.PHYS_ACQ(fmt), G.fir_host(f, mid, None, fmt))
+    found_delayed(peaks, blk, nch, O.group_delay(63))
+
+
+@pytest.mark.parametrize("fmt", [16, 8])
+def test_receiver_with_the_tone_in_band(fmt):
+    """a pass band does not remove an in-band jammer"""
+    mid, _, _ = jammed(fmt, 0.0)
+    f = G.fir_make(float(AO.PHYS_FS), 700e3, 63)
+    peaks, _, _ = G.acquire_host(AO.PHYS_ACQ(fmt), G.fir_host(f, mid, None, fmt))
+    nothing_found(peaks)
+
+
+# ---- structs and the command line --------------------------------------------------------------
+def test_struct_sizes_match_the_c_header(tmp_path):
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gpssim_amd.h"\n'
+                   'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", '
+                   'sizeof(gss_fir_t), sizeof(gss_cli_t), sizeof(gss_run_opts_t), '
+                   'offsetof(gss_cli_t, fir), offsetof(gss_cli_t, has_fir), '
+                   'offsetof(gss_run_opts_t, fir), offsetof(gss_fir_t, n_taps), '
+                   'offsetof(gss_fir_t, pad), offsetof(gss_fir_t, taps));return 0;}\n')
+    exe = tmp_path / "sz"
+    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)],
+                   check=True)
+    got = list(map(int, subprocess.run([str(exe)], capture_output=True, text=True,
+                                       check=True).stdout.split()))
+    assert got == [C.sizeof(G.Fir), C.sizeof(G._Cli), C.sizeof(G._RunOpts), G._Cli.fir.offset,
+                   G._Cli.has_fir.offset, G._RunOpts.fir.offset, G.Fir.n_taps.offset,
+                   G.Fir.pad.offset, G.Fir.taps.offset]
+    assert got[0] == 136 and G.MAXTAP == 64
+
+
+def parse(*args):
+    cli = G._Cli()
+    argv = [b"gps-sdr-sim", b"-e", NAV.encode()] + [a.encode() for a in args]
+    arr = (C.c_char_p * len(argv))(*argv)
+    return G.lib().gss_cli_parse(len(argv), arr, C.byref(cli)), cli
+
+
+def test_cli_bandwidth_forms():
+    rc, cli = parse("-s", "1000000", "-b", "16")
+    assert rc == 0 and cli.has_fir == 0 and cli.has_impair == 0
+    rc, cli = parse("--bandwidth=700000", "-s", "1000000", "-b", "8")   # before -s: the run's rate
+    assert rc == 0 and cli.has_fir == 1 and cli.has_impair == 1
+    assert (cli.impair.sigma_q8, cli.impair.shift, cli.impair.seed) == (0, 0, 0)
+    assert cli.fir.n_taps == 63 and G.Fir.from_buffer_copy(cli.fir).tap_list() == \
+        G.fir_make(1e6, 700e3, 63).tap_list()
+    rc, cli = parse("-s", "1000000", "--bandwidth=5e5,31")
+    assert rc == 0 and G.Fir.from_buffer_copy(cli.fir).tap_list() == \
+        G.fir_make(1e6, 5e5, 31).tap_list()
+    rc, cli = parse("--bandwidth=2e6")                                   # 2.6 MS/s by default
+    assert rc == 0 and G.Fir.from_buffer_copy(cli.fir).tap_list() == \
+        G.fir_make(2.6e6, 2e6, 63).tap_list()
+    # the automatic shift is what it is without the option
+    for extra in (("--cn0=45",), ("--cn0=45", "--jam=cw,30,0"), ("--multipath=all,150,6",)):
+        for b in ("16", "8", "1"):
+            _, a = parse("-s", "1000000", "-b", b, *extra)
+            rc, c = parse("-s", "1000000", "-b", b, "--bandwidth=700000", *extra)
+            assert rc == 0 and c.has_fir == 1
+            assert (c.impair.sigma_q8, c.impair.shift) == (a.impair.sigma_q8, a.impair.shift)
+    rc, cli = parse("-b", "8", "--bandwidth=2e6", "--noise-shift=3")     # accepted with the option
+    assert rc == 0 and cli.impair.shift == 3 and cli.impair.sigma_q8 == 0
+
+
+@pytest.mark.parametrize("args", [
+    ("--bandwidth=",), ("--bandwidth=0",), ("--bandwidth=-1",), ("--bandwidth=2600001",),
+    ("--bandwidth=nan",), ("--bandwidth=inf",), ("--bandwidth=1e6x",), ("--bandwidth=1e6,",),
+    ("--bandwidth=1e6,62",), ("--bandwidth=1e6,65",), ("--bandwidth=1e6,1",),
+    ("--bandwidth=1e6,31.5",), ("--bandwidth=1e6,31,2",), ("--bandwidth=,31",),
+    ("--bandwidth=1e6", "--bandwidth=1e6"), ("--bandwidth=1e6", "--seed=3"),
+    ("--bandwidth=1e6", "--noise-shift=9"),
+])
+def test_cli_bandwidth_errors(args, capfd):
+    rc, cli = parse("-b", "8", "--bandwidth=1e6")            # the well-formed option parses
+    assert rc == 0 and cli.has_fir == 1
+    capfd.readouterr()
+    rc, _ = parse("-b", "8", *args)
+    err = capfd.readouterr().err
+    assert rc == 1
+    assert ("Invalid bandwidth" in err or "--bandwidth given twice" in err or
+            "--noise-shift and --seed need" in err or "Invalid noise shift" in err), err
+
+
+def test_cli_prints_the_filter_and_keeps_the_usage():
+    r = subprocess.run([G.CLI_PATH], capture_output=True, text=True)
+    assert "bandwidth" not in r.stdout + r.stderr                # the reference's usage text
+    # without a GPU the run stops at the device; the line comes before that
+    r = subprocess.run([G.CLI_PATH, "-e", NAV, "-l", "30.286502,120.032669,100", "-d", "0.1", "-s",
+                        "1000000", "--bandwidth=700000", "-o", os.devnull],
+                       capture_output=True, text=True, timeout=120)
+    assert "Filter: taps = 63, delay = 31 samples, noise gain = 0.68928" in r.stderr, r.stderr
+    r = subprocess.run([G.CLI_PATH, "-e", NAV, "-l", "30.286502,120.032669,100", "-d", "0.1", "-s",
+                        "1000000", "--bandwidth=700000", "-o", os.devnull],
+                       capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, WORLD_SIZE="2", RANK="0"))
+    assert r.returncode == 1 and "--bandwidth is not supported" in r.stderr
+
+
+def test_from_cli_sets_fir():
+    scn, out = G.Scenario.from_cli(["-e", NAV, "-l", "30.286502,120.032669,100", "-d", "1",
+                                    "-s", "1000000", "-b", "8", "--bandwidth=700000,31",
+                                    "-o", "x.bin"])
+    assert out == "x.bin" and scn.fir.tap_list() == G.fir_make(1e6, 700e3, 31).tap_list()
+    assert scn.impair.sigma_q8 == 0 and scn.jam is None and scn.echo is None
+    scn.close()
+    scn, _ = G.Scenario.from_cli(["-e", NAV, "-l", "30.286502,120.032669,100", "-d", "1"])
+    assert scn.fir is None and scn.impair is None
+    scn.close()
+
+
+def test_run_node_refuses_the_filter():
+    from gpssim_amd.node import run_node
+    with pytest.raises(ValueError, match="bandwidth"):
+        run_node(["-e", NAV, "-l", "30.286502,120.032669,100", "-d", "1", "--bandwidth=2e6"],
+                 0, 1, 0)
+
+
+# ---- gss_run on the CPU fakes ------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def fake_build(tmp_path_factory):
+    """gss_run.hip and the host plane against tests/helpers' fakes (as tests/test_echo.py), with
+    fir_fake.cpp as the program: once with its filter launch, once without"""
+    if shutil.which("gcc") is None or shutil.which("g++") is None:
+        pytest.skip("gcc/g++ not available")
+    d = tmp_path_factory.mktemp("fir_fake")
+    cf = ["-O2", "-g", "-ffp-contract=off", "-fno-fast-math", "-D_FILE_OFFSET_BITS=64",
+          "-I" + os.path.join(REPO, "include")]
+    inc = ["-I" + os.path.join(REPO, "tests", "helpers"),
+           "-I" + os.path.join(REPO, "tests", "helpers", "fake_hip")]
+    hostdir = os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "host")
+    objs = []
+    srcs = [os.path.join(hostdir, f) for f in sorted(os.listdir(hostdir)) if f.endswith(".c")]
+    srcs.append(os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "cli", "cli_args.c"))
+    for s in srcs:
+        o = str(d / (os.path.basename(s)[:-2] + ".o"))
+        subprocess.run(["gcc"] + cf + ["-c", s, "-o", o], check=True)
+        objs.append(o)
+    cxx = [(os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "hip", "gss_run.hip"), True)]
+    for f in ("fake_hip/fake_hip.cpp", "fake_dev.cpp"):
+        cxx.append((os.path.join(REPO, "tests", "helpers", f), False))
+    for s, as_cxx in cxx:
+        o = str(d / (os.path.basename(s).rsplit(".", 1)[0] + ".o"))
+        subprocess.run(["g++", "-std=c++17"] + cf + inc + (["-x", "c++"] if as_cxx else []) +
+                       ["-c", s, "-o", o], check=True)
+        objs.append(o)
+    exes = {}
+    for name, defs in (("fir_fake", []), ("fir_fake_nolaunch", ["-DNO_LAUNCH"])):
+        o = str(d / (name + ".o"))
+        subprocess.run(["g++", "-std=c++17"] + cf + inc + defs +
+                       ["-c", os.path.join(REPO, "tests", "helpers", "fir_fake.cpp"), "-o", o],
+                       check=True)
+        exes[name] = str(d / name)
+        subprocess.run(["g++", "-o", exes[name]] + objs + [o, "-lm", "-lpthread"], check=True)
+    return exes
+
+
+def test_gss_run_filtered_on_fake_device(fake_build):
+    r = subprocess.run([fake_build["fir_fake"], NAV], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+    assert "argument errors ok" in r.stdout and "all filtered runs ok" in r.stdout
+
+
+def test_gss_run_refuses_the_filter_without_a_launch(fake_build):
+    r = subprocess.run([fake_build["fir_fake_nolaunch"], NAV], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+    assert "refused ok" in r.stdout and "filter launch" in r.stdout
+
+
+def test_fir_check_program(tmp_path):
+    """tests/helpers/fir_check.c without the sanitizers (tools/fir_sanitize.sh runs it with them)"""
+    hostdir = os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "host")
+    srcs = [os.path.join(hostdir, f) for f in sorted(os.listdir(hostdir)) if f.endswith(".c")]
+    exe = str(tmp_path / "fir_check")
+    subprocess.run(["gcc", "-O1", "-ffp-contract=off", "-I" + os.path.join(REPO, "include"), "-o",
+                    exe] + srcs + [os.path.join(REPO, "tests", "helpers", "fir_check.c"), "-lm",
+                                   "-lpthread"], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "fir_check ok" in r.stdout, r.stdout[-4000:]
