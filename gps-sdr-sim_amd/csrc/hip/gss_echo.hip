@@ -1,22 +1,22 @@
 /*
  * gss_echo.hip — multipath echoes added to a render on the GPU (gss_echo_device,
  * include/gpssim_amd.h): one streaming gfx950 kernel over the SC16 samples a render wrote, in
- * place, from the channel rows that render read.  It has the shape of gss_impair.hip's kernel:
+ * place, from the channel rows that render read.  It is the stages' common shape
+ * (gss_stage_dev.h: groups, edges, grid) for SC16 in place, the groups taken a tile at a time:
  *
- *   samples  16-byte loads and stores: 4 samples (I, Q int16) per thread, a tile of 1,024 per
- *            workgroup and trip; grid-stride over the tiles under a cap of 2,048 workgroups
+ *   samples  a tile of 256 groups (1,024 samples) per workgroup and trip; grid-stride over the
+ *            tiles
  *   rows     per tile, the live pairs (echo, channel) of the two blocks it can touch are derived
  *            once by the workgroup's first two waves (one lane per pair, compacted by a ballot)
  *            into LDS, not per thread.  A tile that touches more blocks (blocks shorter than a
  *            tile: tests) derives the rows of the others in each thread, by the same function
- *   tables   the packed cos/sin table (2 KB, built from the handle's tables as in gss_jam.hip)
- *            and the call's C/A chips (4 KB) in LDS; the data words are read from the nav table
+ *   tables   the packed cos/sin table (2 KB) and the call's C/A chips (4 KB) in LDS; the data
+ *            words are read from the nav table
  *   thread   its group is taken on the buffer, so it can straddle a block boundary: the state is
  *            then seeded again from the next block's rows.  Seeding costs one 64-bit multiply
  *            per phase and the split of q by 1023 (32-bit, by constant); the next three samples
  *            are carried (gss_echo_next): no per-sample division, no scratch
- *   edges    the samples before the first 16-byte boundary and after the last whole group go one
- *            at a time through the same arithmetic, each seeded from its own index
+ *   edges    one sample at a time through the same arithmetic, each seeded from its own index
  *   plain    GSS_ECHO_PATH=plain (read per call), and a C/A table of more than 32 rows: one sample
  *            per thread, straight from the definition and global memory (gss_echo_plain_kernel)
  * The arithmetic is csrc/common/gss_echo.h, shared with gss_echo_host.
@@ -27,6 +27,7 @@
 #include <string.h>
 #include "gpssim_amd.h"
 #include "gss_dev.h"
+#include "gss_stage_dev.h"
 #include "../common/gss_echo.h"
 
 extern "C" int gss_echo_args(const gss_echo_t *echo, int n_echo, const void *blk, const void *nch,
@@ -36,9 +37,8 @@ extern "C" int gss_echo_args(const gss_echo_t *echo, int n_echo, const void *blk
 
 namespace {
 
-constexpr int ECHO_THREADS = 256;
-constexpr int ECHO_GRID_MAX = 2048;
-constexpr int ECHO_NS = 4;                              /* samples per thread                  */
+constexpr int ECHO_THREADS = STAGE_THREADS;
+constexpr int ECHO_NS = StageFmt<GSS_FMT_SC16>::NS;     /* samples per thread                  */
 constexpr int ECHO_TILE = ECHO_THREADS * ECHO_NS;       /* samples per workgroup and trip      */
 constexpr int ECHO_BLKS = 2;                            /* blocks whose rows a tile keeps      */
 constexpr int ECHO_PAIRS = GSS_MAXECHO * GSS_MAXCH;     /* one wave: a lane per pair           */
@@ -199,8 +199,7 @@ __device__ __forceinline__ void echo_sample(const EchoArgs &A, const uint32_t *c
 __global__ __launch_bounds__(ECHO_THREADS) void gss_echo_kernel(EchoArgs A)
 {
     __shared__ EchoLds S;
-    for (int i = threadIdx.x; i < GSS_JAM_LUT; i += ECHO_THREADS)
-        S.L[i] = gss_jam_cell(A.lut[i], A.lut[GSS_JAM_LUT + i]);
+    stage_fill_lut(S.L, A.lut);
     for (int i = threadIdx.x; i < A.n_ca * GSS_CA_WORDS; i += ECHO_THREADS)   /* n_ca <= 32 */
         S.CA[i] = A.ca[i];
     if (threadIdx.x == 0) {
@@ -232,12 +231,10 @@ __global__ __launch_bounds__(ECHO_THREADS) void gss_echo_kernel(EchoArgs A)
             echo_group(A, S, b_lo, A.head + g * ECHO_NS);
     }
     __syncthreads();
-    /* the edges: [0, head) and [head + groups * 4, n) */
-    const uint64_t body = A.groups * ECHO_NS, items = A.n - body;
     const uint64_t t0 = (uint64_t)blockIdx.x * ECHO_THREADS + threadIdx.x;
     const uint64_t stride = (uint64_t)gridDim.x * ECHO_THREADS;
-    for (uint64_t e = t0; e < items; e += stride) {
-        const uint64_t j = e < A.head ? e : e + body;
+    for (uint64_t e = t0; e < stage_edge_items<ECHO_NS, 1>(A.n, A.groups); e += stride) {
+        const uint64_t j = stage_edge_at<ECHO_NS, 1>(e, A.head, A.groups);
         int32_t b, s;
         echo_locate(A, j, &b, &s);
         echo_sample(A, S.CA, S.L, j, b, s);
@@ -285,26 +282,14 @@ extern "C" int gss_echo_device(gss_dev *d, const gss_echo_t *echo, int n_echo,
         return gss_fail(GSS_E_ARG, "GSS_ECHO_PATH: '%s' (plain, or unset)", path);
     hipStream_t st = (hipStream_t)stream;
     if (plain) {
-        uint64_t grid = (A.n + ECHO_THREADS - 1) / ECHO_THREADS;
-        grid = grid > ECHO_GRID_MAX ? ECHO_GRID_MAX : grid;
-        hipLaunchKernelGGL(gss_echo_plain_kernel, dim3((unsigned)grid), dim3(ECHO_THREADS), 0, st, A);
+        hipLaunchKernelGGL(gss_echo_plain_kernel, dim3(gss_stage_grid(A.n, 0, ECHO_THREADS)),
+                           dim3(ECHO_THREADS), 0, st, A);
     } else {
-        /* the least head after which the samples are 16-byte aligned; none (a base that is not a
-           multiple of 4 bytes): every sample by the edges */
-        A.head = A.n;
-        A.groups = 0;
-        for (uint64_t h = 0; h < 4 && h <= A.n; h++)
-            if (((uintptr_t)iq + 4 * h) % 16 == 0) {
-                A.head = h;
-                A.groups = (A.n - h) / ECHO_NS;
-                break;
-            }
-        const uint64_t tiles = (A.groups + ECHO_THREADS - 1) / ECHO_THREADS;
-        const uint64_t items = A.n - A.groups * ECHO_NS;
-        const uint64_t eg = (items + ECHO_THREADS - 1) / ECHO_THREADS;
-        uint64_t grid = tiles > eg ? tiles : eg;
-        grid = grid < 1 ? 1 : grid > ECHO_GRID_MAX ? ECHO_GRID_MAX : grid;
-        hipLaunchKernelGGL(gss_echo_kernel, dim3((unsigned)grid), dim3(ECHO_THREADS), 0, st, A);
+        /* in place: a base that is not a multiple of 4 bytes leaves every sample to the edges */
+        gss_stage_split((uintptr_t)iq, (uintptr_t)iq, A.n, GSS_FMT_SC16, &A.head, &A.groups);
+        const unsigned grid = gss_stage_grid(A.groups, gss_stage_items(A.n, A.groups, GSS_FMT_SC16),
+                                             ECHO_THREADS);
+        hipLaunchKernelGGL(gss_echo_kernel, dim3(grid), dim3(ECHO_THREADS), 0, st, A);
     }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : gss_fail(GSS_E_HIP, "echo kernel: %s", hipGetErrorString(e));

@@ -1,11 +1,10 @@
 /*
  * gss_fir.hip — the front-end band-limit filter on the GPU (gss_fir_device,
  * include/gpssim_amd.h): one gfx950 kernel per output format over the SC16 samples that the
- * impairment or the jammers wrote, out of place.  It takes the outer shape of gss_impair.hip:
+ * impairment or the jammers wrote, out of place.  It is the stages' common shape
+ * (gss_stage_dev.h: groups, edges, grid), the groups taken a tile at a time:
  *
- *   samples  a tile of 256 groups per workgroup and trip (a group: 4, 8 or 16 samples for SC16,
- *            SC08, SC01: one 16-byte store, or one dword of bits); grid-stride over the tiles
- *            under a cap of 2,048 workgroups
+ *   samples  a tile of 256 groups per workgroup and trip; grid-stride over the tiles
  *   staging  the tile and the 64 samples before it go into LDS once, de-interleaved: one array
  *            of 32-bit words per component, a word holding two consecutive samples.  The tile
  *            itself by 16-byte loads; the 64 samples before it one per lane, from the input,
@@ -16,9 +15,8 @@
  *   taps     paired on the host for both parities of an output's distance to a word
  *            (gss_fir_pairs) and passed by value: every index into them is a constant of the
  *            unrolled loop, which leaves at a wave-uniform test on n_taps
- *   edges    the samples before the first 16-byte boundary of the input (and of the output's
- *            store width) and after the last whole group go one by one (SC01: byte by byte)
- *            through the definition, from global memory.  An input that is not 4-byte aligned,
+ *   edges    an item at a time through the definition, from global memory.  An input that is
+ *            not 4-byte aligned,
  *            or an input and output whose boundaries never coincide, has no whole group: the
  *            call is then all edges, at the plain form's speed (18 to 46 times slower at the
  *            headline window).  gss_run's buffers are aligned
@@ -32,6 +30,7 @@
 #include <string.h>
 #include "gpssim_amd.h"
 #include "gss_dev.h"
+#include "gss_stage_dev.h"
 #include "../common/gss_fir.h"
 
 extern "C" int gss_fir_args(const gss_fir_t *fir, const void *in, const void *halo, size_t n,
@@ -39,8 +38,7 @@ extern "C" int gss_fir_args(const gss_fir_t *fir, const void *in, const void *ha
 
 namespace {
 
-constexpr int FIR_THREADS = 256;
-constexpr int FIR_GRID_MAX = 2048;
+constexpr int FIR_THREADS = STAGE_THREADS;
 constexpr int FIR_HIST = GSS_MAXTAP;            /* samples staged before a tile (>= T - 1)      */
 
 struct FirArgs {
@@ -52,11 +50,6 @@ struct FirArgs {
     int32_t n_taps;
     uint32_t even[GSS_FIR_NE], odd[GSS_FIR_NO];      /* gss_fir_pairs                           */
 };
-
-template <int FMT> struct FirFmt;
-template <> struct FirFmt<GSS_FMT_SC16> { static constexpr int NS = 4, ITEM = 1; };
-template <> struct FirFmt<GSS_FMT_SC08> { static constexpr int NS = 8, ITEM = 1; };
-template <> struct FirFmt<GSS_FMT_SC01> { static constexpr int NS = 16, ITEM = 4; };
 
 typedef short fir_s2 __attribute__((ext_vector_type(2)));
 
@@ -92,61 +85,18 @@ __device__ __forceinline__ void fir_sample(const FirArgs &A, uint64_t j, int32_t
 /* one edge item: a sample (SC16, SC08) or the 4 samples of a byte (SC01) at index j */
 template <int FMT> __device__ __forceinline__ void fir_item(const FirArgs &A, uint64_t j)
 {
-    uint32_t byte = 0;
+    constexpr int ITEM = StageFmt<FMT>::ITEM;
+    int32_t v[2 * ITEM];
 #pragma unroll
-    for (int s = 0; s < FirFmt<FMT>::ITEM; s++) {
-        int32_t vi, vq;
-        fir_sample(A, j + s, &vi, &vq);
-        if constexpr (FMT == GSS_FMT_SC16) {
-            ((int16_t *)A.out)[2 * j] = (int16_t)gss_imp_sc16(vi);
-            ((int16_t *)A.out)[2 * j + 1] = (int16_t)gss_imp_sc16(vq);
-        } else if constexpr (FMT == GSS_FMT_SC08) {
-            ((int8_t *)A.out)[2 * j] = (int8_t)gss_imp_sc08(vi);
-            ((int8_t *)A.out)[2 * j + 1] = (int8_t)gss_imp_sc08(vq);
-        } else {
-            byte |= (vi > 0 ? 1u : 0u) << (7 - 2 * s) | (vq > 0 ? 1u : 0u) << (6 - 2 * s);
-        }
-    }
-    if constexpr (FMT == GSS_FMT_SC01)
-        ((uint8_t *)A.out)[j / 4] = (uint8_t)byte;
-}
-
-/* the group's 2 NS rounded values (I, Q interleaved) to A.out at sample j */
-template <int FMT>
-__device__ __forceinline__ void fir_store(const FirArgs &A, uint64_t j,
-                                          const int32_t (&v)[2 * FirFmt<FMT>::NS])
-{
-    constexpr int NS = FirFmt<FMT>::NS;
-    if constexpr (FMT == GSS_FMT_SC16) {
-        uint32_t o[4];
-#pragma unroll
-        for (int s = 0; s < 4; s++)
-            o[s] = ((uint32_t)gss_imp_sc16(v[2 * s]) & 0xFFFFu) |
-                   ((uint32_t)gss_imp_sc16(v[2 * s + 1]) << 16);
-        *reinterpret_cast<uint4 *>((int16_t *)A.out + 2 * j) = make_uint4(o[0], o[1], o[2], o[3]);
-    } else if constexpr (FMT == GSS_FMT_SC08) {
-        uint32_t o[4];
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            o[d] = 0;
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-                o[d] |= ((uint32_t)gss_imp_sc08(v[4 * d + b]) & 0xFFu) << (8 * b);
-        }
-        *reinterpret_cast<uint4 *>((int8_t *)A.out + 2 * j) = make_uint4(o[0], o[1], o[2], o[3]);
-    } else {
-        uint32_t o = 0;                                /* component i -> byte i / 8, bit 7 - i % 8 */
-#pragma unroll
-        for (int i = 0; i < 2 * NS; i++)
-            o |= (v[i] > 0 ? 1u : 0u) << (8 * (i / 8) + 7 - (i % 8));
-        *reinterpret_cast<uint32_t *>((uint8_t *)A.out + j / 4) = o;
-    }
+    for (int s = 0; s < ITEM; s++)
+        fir_sample(A, j + s, &v[2 * s], &v[2 * s + 1]);
+    stage_store_item<FMT>(A.out, j, v);
 }
 
 template <int FMT>
 __global__ __launch_bounds__(FIR_THREADS) void gss_fir_kernel(FirArgs A)
 {
-    constexpr int NS = FirFmt<FMT>::NS, ITEM = FirFmt<FMT>::ITEM;
+    constexpr int NS = StageFmt<FMT>::NS, ITEM = StageFmt<FMT>::ITEM;
     constexpr int TILE = FIR_THREADS * NS;               /* samples per workgroup and trip      */
     constexpr int WORDS = (FIR_HIST + TILE) / 2;         /* per component                       */
     constexpr int WIN = FIR_HIST / 2 + NS / 2;           /* a thread's window, words            */
@@ -214,22 +164,18 @@ __global__ __launch_bounds__(FIR_THREADS) void gss_fir_kernel(FirArgs A)
 #pragma unroll
         for (int i = 0; i < 2 * NS; i++)
             v[i] = gss_fir_round(acc[i]);
-        fir_store<FMT>(A, base + (uint64_t)tid * NS, v);
+        stage_store_group<FMT>(A.out, base + (uint64_t)tid * NS, v);
     }
-    /* the edges: [0, head) and [head + groups * NS, n) */
-    const uint64_t body = A.groups * NS, items = (A.n - body) / ITEM;
     const uint64_t t0 = (uint64_t)blockIdx.x * FIR_THREADS + tid;
     const uint64_t stride = (uint64_t)gridDim.x * FIR_THREADS;
-    for (uint64_t e = t0; e < items; e += stride) {
-        const uint64_t j = e * ITEM;
-        fir_item<FMT>(A, j < A.head ? j : j + body);
-    }
+    for (uint64_t e = t0; e < stage_edge_items<NS, ITEM>(A.n, A.groups); e += stride)
+        fir_item<FMT>(A, stage_edge_at<NS, ITEM>(e, A.head, A.groups));
 }
 
 template <int FMT>
 __global__ __launch_bounds__(FIR_THREADS) void gss_fir_plain_kernel(FirArgs A)
 {
-    constexpr int ITEM = FirFmt<FMT>::ITEM;
+    constexpr int ITEM = StageFmt<FMT>::ITEM;
     const uint64_t t0 = (uint64_t)blockIdx.x * FIR_THREADS + threadIdx.x;
     const uint64_t stride = (uint64_t)gridDim.x * FIR_THREADS;
     for (uint64_t e = t0; e < A.n / ITEM; e += stride)
@@ -260,44 +206,16 @@ extern "C" int gss_fir_device(gss_dev *d, const gss_fir_t *fir, const int16_t *i
         return gss_fail(GSS_E_ARG, "GSS_FIR_PATH: '%s' (plain, or unset)", path);
     if (hipSetDevice(d->ordinal) != hipSuccess)
         return gss_fail(GSS_E_HIP, "hipSetDevice failed");
-    const size_t ns = fmt == GSS_FMT_SC16 ? 4 : fmt == GSS_FMT_SC08 ? 8 : 16;
-    const int item = fmt == GSS_FMT_SC01 ? 4 : 1;
     FirArgs A;
     memset(&A, 0, sizeof A);
     A.in = in; A.halo = halo; A.out = out; A.n = n; A.n_taps = fir->n_taps;
     gss_fir_pairs(fir, A.even, A.odd);
-    uint64_t grid;
-    if (plain) {
-        grid = (n / (uint64_t)item + FIR_THREADS - 1) / FIR_THREADS;
-    } else {
-        /* the least head after which the input is 16-byte aligned and the output aligned to its
-           store (16, 16, 4 bytes); none (pointers that never line up): every sample by the edges */
-        A.head = n;
-        A.groups = 0;
-        for (size_t h = 0; h < 16 && h <= n; h += (size_t)item) {
-            const uintptr_t ai = (uintptr_t)in + 4 * h;
-            const uintptr_t ao = (uintptr_t)out + (fmt == GSS_FMT_SC16   ? 4 * h
-                                                   : fmt == GSS_FMT_SC08 ? 2 * h
-                                                                         : h / 4);
-            if (ai % 16 == 0 && ao % (fmt == GSS_FMT_SC01 ? 4 : 16) == 0) {
-                A.head = h;
-                A.groups = (n - h) / ns;
-                break;
-            }
-        }
-        const uint64_t tiles = (A.groups + FIR_THREADS - 1) / FIR_THREADS;
-        const uint64_t items = (n - A.groups * ns) / (uint64_t)item;
-        const uint64_t eg = (items + FIR_THREADS - 1) / FIR_THREADS;
-        grid = tiles > eg ? tiles : eg;
-    }
-    grid = grid < 1 ? 1 : grid > FIR_GRID_MAX ? FIR_GRID_MAX : grid;
-    hipStream_t st = (hipStream_t)stream;
-    if (fmt == GSS_FMT_SC16)
-        launch<GSS_FMT_SC16>(A, plain, (unsigned)grid, st);
-    else if (fmt == GSS_FMT_SC08)
-        launch<GSS_FMT_SC08>(A, plain, (unsigned)grid, st);
-    else
-        launch<GSS_FMT_SC01>(A, plain, (unsigned)grid, st);
+    if (!plain)                                     /* plain: head 0, no group, n / item items */
+        gss_stage_split((uintptr_t)in, (uintptr_t)out, n, fmt, &A.head, &A.groups);
+    const unsigned grid = gss_stage_grid(A.groups, gss_stage_items(n, A.groups, fmt), FIR_THREADS);
+    stage_dispatch(fmt, [&](auto F) {
+        launch<decltype(F)::value>(A, plain, grid, (hipStream_t)stream);
+    });
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : gss_fail(GSS_E_HIP, "filter kernel: %s", hipGetErrorString(e));
 }

@@ -11,6 +11,7 @@
 #include <string.h>
 #include "gss_host.h"
 #include "../common/gss_fir.h"
+#include "../common/gss_stage.h"
 
 int gss_fir_check(const gss_fir_t *fir)
 {
@@ -40,7 +41,7 @@ int gss_fir_args(const gss_fir_t *fir, const void *in, const void *halo, size_t 
         return gss_fail(GSS_E_ARG, "invalid filter buffers");
     /* out of place: an output sample is read again by the T - 1 outputs after it */
     const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-    const size_t nb = fmt == GSS_FMT_SC16 ? n * 4 : fmt == GSS_FMT_SC08 ? n * 2 : n / 4;
+    const size_t nb = gss_fmt_bytes(n, fmt);
     if (a < b + nb && b < a + n * 4)
         return gss_fail(GSS_E_ARG, "filter output overlaps its input");
     const uintptr_t h = (uintptr_t)halo;
@@ -62,17 +63,7 @@ int gss_fir_host(const gss_fir_t *fir, const int16_t *in, const int16_t *halo, s
             int32_t acc = 0;
             for (int k = 0; k < T; k++)
                 acc += (int32_t)fir->taps[k] * gss_fir_x(in, halo, T, (int64_t)j - k, c);
-            const int32_t v = gss_fir_round(acc);
-            if (fmt == GSS_FMT_SC16) {
-                ((int16_t *)out)[2 * j + c] = (int16_t)gss_imp_sc16(v);
-            } else if (fmt == GSS_FMT_SC08) {
-                ((int8_t *)out)[2 * j + c] = (int8_t)gss_imp_sc08(v);
-            } else {                                   /* gpssim.c:2268-2274, MSB first */
-                const int bit = (int)((2 * j + c) & 7);
-                byte = (uint8_t)((bit ? byte : 0) | ((v > 0 ? 1 : 0) << (7 - bit)));
-                if (bit == 7)
-                    ((uint8_t *)out)[(2 * j + c) >> 3] = byte;
-            }
+            gss_imp_put(out, fmt, 2 * j + c, gss_fir_round(acc), &byte);
         }
     return 0;
 }

@@ -9,7 +9,7 @@
 #include <pthread.h>
 #include <string.h>
 #include "gss_host.h"
-#include "../common/gss_impair.h"
+#include "../common/gss_stage.h"
 
 /* The standard normal quantile: Wichura, "Algorithm AS241: The Percentage Points of the Normal
    Distribution", Applied Statistics 37 (1988), routine PPND16 (relative error ~1e-16).  Only
@@ -96,7 +96,7 @@ int gss_impair_check(const gss_impair_t *p, const void *iq, uint64_t sample0, si
         return gss_fail(GSS_E_ARG, "invalid impairment buffers");
     /* in place for SC16 only; any other overlap would read samples already overwritten */
     const uintptr_t a = (uintptr_t)iq, b = (uintptr_t)out;
-    const size_t nb = fmt == GSS_FMT_SC16 ? n * 4 : fmt == GSS_FMT_SC08 ? n * 2 : n / 4;
+    const size_t nb = gss_fmt_bytes(n, fmt);
     if (a < b + nb && b < a + n * 4 && !(fmt == GSS_FMT_SC16 && a == b))
         return gss_fail(GSS_E_ARG, "impairment output overlaps its input (in place: SC16 only)");
     return 0;
@@ -118,17 +118,7 @@ int gss_impair_host(const gss_impair_t *p, const int16_t *iq, uint64_t sample0, 
             gss_imp_philox((uint32_t)(a >> 1), (uint32_t)(a >> 33), k0, k1, w);
         for (int c = 0; c < 2; c++) {
             const int32_t g = gss_imp_noise(w[2 * (a & 1) + c], noise_tbl, p->sigma_q8);
-            const int32_t v = gss_imp_level(iq[2 * j + c], g, p->shift);
-            if (fmt == GSS_FMT_SC16) {
-                ((int16_t *)out)[2 * j + c] = (int16_t)gss_imp_sc16(v);
-            } else if (fmt == GSS_FMT_SC08) {
-                ((int8_t *)out)[2 * j + c] = (int8_t)gss_imp_sc08(v);
-            } else {                                   /* gpssim.c:2268-2274, MSB first */
-                const int bit = (int)((2 * j + c) & 7);
-                byte = (uint8_t)((bit ? byte : 0) | ((v > 0 ? 1 : 0) << (7 - bit)));
-                if (bit == 7)
-                    ((uint8_t *)out)[(2 * j + c) >> 3] = byte;
-            }
+            gss_imp_put(out, fmt, 2 * j + c, gss_imp_level(iq[2 * j + c], g, p->shift), &byte);
         }
     }
     return 0;

@@ -10,7 +10,7 @@
 #include <pthread.h>
 #include <string.h>
 #include "gss_host.h"
-#include "../common/gss_impair.h"
+#include "../common/gss_stage.h"
 #include "../common/gss_jam.h"
 
 int gss_impair_check(const gss_impair_t *p, const void *iq, uint64_t sample0, size_t n, int fmt,
@@ -70,17 +70,8 @@ int gss_jam_host(const gss_impair_t *p, const gss_jam_t *jam, int n_jam, const i
         }
         for (int c = 0; c < 2; c++) {
             const int32_t g = gss_imp_noise(w[2 * (a & 1) + c], jam_noise, p->sigma_q8);
-            const int32_t v = gss_imp_level(iq[2 * j + c] + jc[c], g, p->shift);
-            if (fmt == GSS_FMT_SC16) {
-                ((int16_t *)out)[2 * j + c] = (int16_t)gss_imp_sc16(v);
-            } else if (fmt == GSS_FMT_SC08) {
-                ((int8_t *)out)[2 * j + c] = (int8_t)gss_imp_sc08(v);
-            } else {                                   /* gpssim.c:2268-2274, MSB first */
-                const int bit = (int)((2 * j + c) & 7);
-                byte = (uint8_t)((bit ? byte : 0) | ((v > 0 ? 1 : 0) << (7 - bit)));
-                if (bit == 7)
-                    ((uint8_t *)out)[(2 * j + c) >> 3] = byte;
-            }
+            gss_imp_put(out, fmt, 2 * j + c, gss_imp_level(iq[2 * j + c] + jc[c], g, p->shift),
+                        &byte);
         }
     }
     return 0;

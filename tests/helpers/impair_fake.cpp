@@ -1,74 +1,20 @@
 /*
  * impair_fake.cpp — gss_run with additive noise (gss_run_opts_t.impair) on the CPU fakes of
- * tests/helpers (fake_hip, fake_dev.cpp; see run_fake.cpp).  The impairment's launch is supplied
- * here: gss_impair_host queued on the stream.  For each format the bytes of an impaired run must
+ * tests/helpers (fake_hip, fake_dev.cpp; see run_fake.cpp).  The impairment's launch is stage_fake.h's:
+ * gss_impair_host queued on the stream.  For each format the bytes of an impaired run must
  * be gss_impair_host over the bytes of the plain SC16 run of the same scenario, whatever the
  * batch and the proof mode (the redo of rejected blocks included).  Built with -DNO_LAUNCH the
  * launch is absent and the run must refuse with GSS_E_STATE.  Test infrastructure only.
  *
  * usage: impair_fake NAV_FILE
  */
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
-#include <hip/hip_runtime.h>
-#include "gpssim_amd.h"
-#include "fake_dev.h"
-
-#ifndef NO_LAUNCH
-extern "C" int gss_impair_device(gss_dev *d, const gss_impair_t *p, const int16_t *iq,
-                                 uint64_t sample0, size_t n, int fmt, void *out, void *stream)
-{
-    if (!d || !p || !iq || !out)
-        return GSS_E_ARG;
-    const gss_impair_t imp = *p;
-    fake_enqueue((hipStream_t)stream, [=] {
-        if (gss_impair_host(&imp, iq, sample0, n, fmt, out))
-            abort();
-    });
-    return 0;
-}
+#ifdef NO_LAUNCH
+#define STAGE_FAKE_NO_IMPAIR
 #endif
+#include "stage_fake.h"
 
 static const char *g_nav;
-
-static gss_scn *open_scn(double fs, int fmt)
-{
-    gss_opts_t o;
-    memset(&o, 0, sizeof o);
-    o.nav_file = g_nav;
-    o.has_llh = 1;
-    o.llh[0] = 30.286502;
-    o.llh[1] = 120.032669;
-    o.llh[2] = 100.0;
-    o.samp_freq = fs;
-    o.data_format = fmt;
-    o.duration = 3.0;
-    o.quiet = 1;
-    gss_scn *s = nullptr;
-    if (gss_scn_open(&s, &o)) {
-        fprintf(stderr, "scenario: %s\n", gss_last_error());
-        exit(2);
-    }
-    return s;
-}
-
-struct Sink {
-    std::vector<uint8_t> bytes;
-    int64_t next = 0;
-    int bad = 0;
-};
-
-static int sink(void *user, const void *bytes, size_t n, int64_t first, int nb)
-{
-    Sink *k = (Sink *)user;
-    if (first != k->next)
-        k->bad++;
-    k->next = first + nb;
-    k->bytes.insert(k->bytes.end(), (const uint8_t *)bytes, (const uint8_t *)bytes + n);
-    return 0;
-}
+static gss_scn *open_scn(double fs, int fmt) { return open_scn(g_nav, fs, fmt, 3.0); }
 
 int main(int argc, char **argv)
 {
@@ -96,7 +42,7 @@ int main(int argc, char **argv)
     }
 #else
     struct Case { double fs; int fmt; } cases[] = {{1000010.0, 16}, {1000010.0, 8}, {1.0e6, 1}};
-    struct Mode { const char *name, *proof, *exact, *late; int batch; } modes[] = {
+    const Mode modes[] = {
         {"default", nullptr, nullptr, nullptr, 8},
         {"device proofs, every 3rd exact", "gpu", "3", "0", 5},
         {"device proofs, every 3rd exact, redo", "gpu", "3", "1", 64},
@@ -114,17 +60,13 @@ int main(int argc, char **argv)
             return 1;
         }
         const size_t n = plain.bytes.size() / 4;
-        std::vector<uint8_t> want(c.fmt == 16 ? n * 4 : c.fmt == 8 ? n * 2 : n / 4);
+        std::vector<uint8_t> want(gss_fmt_bytes(n, c.fmt));
         if (gss_impair_host(&imp, (const int16_t *)plain.bytes.data(), 0, n, c.fmt, want.data())) {
             printf("host impairment: %s\n", gss_last_error());
             return 1;
         }
         for (const Mode &m : modes) {
-            for (const char *key : {"GSS_RUN_PROOF", "GSS_RUN_FORCE_EXACT", "GSS_RUN_LATE_VERDICTS"})
-                unsetenv(key);
-            if (m.proof) setenv("GSS_RUN_PROOF", m.proof, 1);
-            if (m.exact) setenv("GSS_RUN_FORCE_EXACT", m.exact, 1);
-            if (m.late) setenv("GSS_RUN_LATE_VERDICTS", m.late, 1);
+            stage_mode_env(&m);
             Sink k;
             s = open_scn(c.fs, c.fmt);
             rc = gss_run_ex(d, s, 0, -1, m.batch, 2, sink, &k, &ro);

@@ -5,13 +5,13 @@ code-phase bias an echo gives a tracking loop against the multipath error envelo
 command-line option, and gss_run with echoes on the CPU fakes of tests/helpers (echo_fake.cpp)."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import NAV, REPO
+from fake_build import programs
 
 import gpssim_amd as G
 import echo_oracle as O
@@ -369,40 +369,8 @@ def test_struct_sizes_match_the_c_header(tmp_path):
 # ---- gss_run on the CPU fakes ------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def fake_build(tmp_path_factory):
-    """gss_run.hip and the host plane against tests/helpers' fakes (as tests/test_jam.py), with
-    echo_fake.cpp as the program: once with its echo launch, once without"""
-    if shutil.which("gcc") is None or shutil.which("g++") is None:
-        pytest.skip("gcc/g++ not available")
-    d = tmp_path_factory.mktemp("echo_fake")
-    cf = ["-O2", "-g", "-ffp-contract=off", "-fno-fast-math", "-D_FILE_OFFSET_BITS=64",
-          "-I" + os.path.join(REPO, "include")]
-    inc = ["-I" + os.path.join(REPO, "tests", "helpers"),
-           "-I" + os.path.join(REPO, "tests", "helpers", "fake_hip")]
-    hostdir = os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "host")
-    objs = []
-    srcs = [os.path.join(hostdir, f) for f in sorted(os.listdir(hostdir)) if f.endswith(".c")]
-    srcs.append(os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "cli", "cli_args.c"))
-    for s in srcs:
-        o = str(d / (os.path.basename(s)[:-2] + ".o"))
-        subprocess.run(["gcc"] + cf + ["-c", s, "-o", o], check=True)
-        objs.append(o)
-    cxx = [(os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "hip", "gss_run.hip"), True)]
-    for f in ("fake_hip/fake_hip.cpp", "fake_dev.cpp"):
-        cxx.append((os.path.join(REPO, "tests", "helpers", f), False))
-    for s, as_cxx in cxx:
-        o = str(d / (os.path.basename(s).rsplit(".", 1)[0] + ".o"))
-        subprocess.run(["g++", "-std=c++17"] + cf + inc + (["-x", "c++"] if as_cxx else []) +
-                       ["-c", s, "-o", o], check=True)
-        objs.append(o)
-    exes = {}
-    for name, defs in (("echo_fake", []), ("echo_fake_nolaunch", ["-DNO_LAUNCH"])):
-        o = str(d / (name + ".o"))
-        subprocess.run(["g++", "-std=c++17"] + cf + inc + defs +
-                       ["-c", os.path.join(REPO, "tests", "helpers", "echo_fake.cpp"), "-o", o],
-                       check=True)
-        exes[name] = str(d / name)
-        subprocess.run(["g++", "-o", exes[name]] + objs + [o, "-lm", "-lpthread"], check=True)
-    return exes
+    """echo_fake.cpp on the CPU fakes (tests/fake_build.py): with its launch, and without"""
+    return programs(tmp_path_factory, "echo_fake")
 
 
 def test_gss_run_echoed_on_fake_device(fake_build):

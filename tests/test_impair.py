@@ -4,7 +4,6 @@ tests/impair_oracle.py byte for byte, the statistics of the draws, the command-l
 gss_run with the impairment on the CPU fakes of tests/helpers (impair_fake.cpp)."""
 import ctypes as C
 import os
-import shutil
 import statistics
 import subprocess
 
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import NAV, REPO
+from fake_build import programs
 
 import gpssim_amd as G
 import impair_oracle as O
@@ -179,40 +179,8 @@ def test_run_node_refuses_noise_options():
 
 @pytest.fixture(scope="module")
 def fake_build(tmp_path_factory):
-    """gss_run.hip and the host plane against tests/helpers' fakes (as tests/test_run_fake.py),
-    with impair_fake.cpp as the program: once with its impairment launch, once without"""
-    if shutil.which("gcc") is None or shutil.which("g++") is None:
-        pytest.skip("gcc/g++ not available")
-    d = tmp_path_factory.mktemp("impair_fake")
-    cf = ["-O2", "-g", "-ffp-contract=off", "-fno-fast-math", "-D_FILE_OFFSET_BITS=64",
-          "-I" + os.path.join(REPO, "include")]
-    inc = ["-I" + os.path.join(REPO, "tests", "helpers"),
-           "-I" + os.path.join(REPO, "tests", "helpers", "fake_hip")]
-    host = os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "host")
-    objs = []
-    srcs = [os.path.join(host, f) for f in sorted(os.listdir(host)) if f.endswith(".c")]
-    srcs.append(os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "cli", "cli_args.c"))
-    for s in srcs:
-        o = str(d / (os.path.basename(s)[:-2] + ".o"))
-        subprocess.run(["gcc"] + cf + ["-c", s, "-o", o], check=True)
-        objs.append(o)
-    cxx = [(os.path.join(REPO, "gps-sdr-sim_amd", "csrc", "hip", "gss_run.hip"), True)]
-    for f in ("fake_hip/fake_hip.cpp", "fake_dev.cpp"):
-        cxx.append((os.path.join(REPO, "tests", "helpers", f), False))
-    for s, as_cxx in cxx:
-        o = str(d / (os.path.basename(s).rsplit(".", 1)[0] + ".o"))
-        subprocess.run(["g++", "-std=c++17"] + cf + inc + (["-x", "c++"] if as_cxx else []) +
-                       ["-c", s, "-o", o], check=True)
-        objs.append(o)
-    exes = {}
-    for name, defs in (("impair_fake", []), ("impair_fake_nolaunch", ["-DNO_LAUNCH"])):
-        o = str(d / (name + ".o"))
-        subprocess.run(["g++", "-std=c++17"] + cf + inc + defs +
-                       ["-c", os.path.join(REPO, "tests", "helpers", "impair_fake.cpp"), "-o", o],
-                       check=True)
-        exes[name] = str(d / name)
-        subprocess.run(["g++", "-o", exes[name]] + objs + [o, "-lm", "-lpthread"], check=True)
-    return exes
+    """impair_fake.cpp on the CPU fakes (tests/fake_build.py): with its launch, and without"""
+    return programs(tmp_path_factory, "impair_fake")
 
 
 def test_gss_run_impaired_on_fake_device(fake_build):
@@ -227,3 +195,14 @@ def test_gss_run_refuses_noise_without_a_launch(fake_build):
                        timeout=600)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
     assert "refused ok" in r.stdout and "impairment launch" in r.stdout
+
+
+def test_stage_split_check_program(tmp_path):
+    """tests/helpers/stage_split_check.c: the head/groups split the stages' launches share
+    (csrc/common/gss_stage.h), by its properties over every format, offset and small n, with
+    gss_fmt_bytes, gss_stage_grid and gss_imp_put"""
+    exe = str(tmp_path / "stage_split_check")
+    subprocess.run(["gcc", "-O1", "-Wall", "-Werror", "-I" + os.path.join(REPO, "include"), "-o", exe,
+                    os.path.join(REPO, "tests", "helpers", "stage_split_check.c")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "stage_split_check ok" in r.stdout, r.stdout[-4000:]

@@ -10,10 +10,11 @@ runs the same program under TSan and ASan+UBSan; this is the plain build, so the
 catches an orchestration regression without a GPU.
 """
 import os
-import shutil
 import subprocess
 
 import pytest
+
+from fake_build import programs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAV = os.path.join(ROOT, "tests", "golden", "data", "brdc3540.14n")
@@ -21,32 +22,7 @@ NAV = os.path.join(ROOT, "tests", "golden", "data", "brdc3540.14n")
 
 @pytest.fixture(scope="module")
 def run_fake(tmp_path_factory):
-    if shutil.which("gcc") is None or shutil.which("g++") is None:
-        pytest.skip("gcc/g++ not available")
-    d = tmp_path_factory.mktemp("fake")
-    cf = ["-O2", "-g", "-ffp-contract=off", "-fno-fast-math", "-D_FILE_OFFSET_BITS=64",
-          "-I" + os.path.join(ROOT, "include")]
-    inc = ["-I" + os.path.join(ROOT, "tests", "helpers"),
-           "-I" + os.path.join(ROOT, "tests", "helpers", "fake_hip")]
-    host = os.path.join(ROOT, "gps-sdr-sim_amd", "csrc", "host")
-    objs = []
-    srcs = [os.path.join(host, f) for f in sorted(os.listdir(host)) if f.endswith(".c")]
-    srcs.append(os.path.join(ROOT, "gps-sdr-sim_amd", "csrc", "cli", "cli_args.c"))
-    for s in srcs:
-        o = str(d / (os.path.basename(s)[:-2] + ".o"))
-        subprocess.run(["gcc"] + cf + ["-c", s, "-o", o], check=True)
-        objs.append(o)
-    cxx = [(os.path.join(ROOT, "gps-sdr-sim_amd", "csrc", "hip", "gss_run.hip"), True)]
-    for f in ("fake_hip/fake_hip.cpp", "fake_dev.cpp", "run_fake.cpp"):
-        cxx.append((os.path.join(ROOT, "tests", "helpers", f), False))
-    for s, as_cxx in cxx:
-        o = str(d / (os.path.basename(s).rsplit(".", 1)[0] + ".o"))
-        cmd = ["g++", "-std=c++17"] + cf + inc + (["-x", "c++"] if as_cxx else []) + ["-c", s, "-o", o]
-        subprocess.run(cmd, check=True)
-        objs.append(o)
-    exe = str(d / "run_fake")
-    subprocess.run(["g++", "-o", exe] + objs + ["-lm", "-lpthread"], check=True)
-    return exe
+    return programs(tmp_path_factory, "run_fake", nolaunch=False)["run_fake"]
 
 
 @pytest.mark.parametrize("args", [("35", "64", "1"), ("25", "16", "8")])

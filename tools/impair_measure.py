@@ -4,7 +4,7 @@ its share of the HBM roofline at each format, and the wall time of the 300 s -b 
 CLI runs with --cn0=45 against the same commands without it, interleaved (GSS_PARENT_CLI: the
 gps-sdr-sim of another build, e.g. the parent commit's, run beside them).
 
-usage: python tools/impair_measure.py [--cli-only]"""
+usage: python tools/impair_measure.py [--cli-only | --kernels-only]"""
 import os, subprocess, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "gps-sdr-sim_amd"))
@@ -78,6 +78,8 @@ def kernels():
 
 if not CLI_ONLY:
     kernels()
+if "--kernels-only" in sys.argv:
+    sys.exit(0)
 
 # (3) CLI wall times, parent build (plain) and this build (plain, --cn0=45), interleaved
 new = G.CLI_PATH
