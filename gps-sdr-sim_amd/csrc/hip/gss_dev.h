@@ -4,7 +4,8 @@
  * the scratch of the acquisition search and of tracking.  Everything here belongs to one handle
  * and is released by gss_dev_close; a handle is not thread-safe.
  *
- * gss_run.hip does not include this header: it is also built against the test fake's own
+ * The streaming driver (gss_run.hip, gss_run_plan.hip, gss_run_pool.hip) does not include this
+ * header: it is also built against the test fake's own
  * struct gss_dev and reaches the handle through gss_dev_ordinal alone.
  */
 #ifndef GSS_DEV_H

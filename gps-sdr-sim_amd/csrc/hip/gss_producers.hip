@@ -500,7 +500,7 @@ extern "C" int gss_spec_device(gss_dev *d, gss_spec_in_t *in, int nrow, int n_pe
     return e == hipSuccess ? 0 : gss_fail(GSS_E_HIP, "spec kernel: %s", hipGetErrorString(e));
 }
 
-/* gss_run's uploads of its slots' inputs (gss_run.hip, dev_copy): 16-byte vector loads, four in
+/* gss_run's uploads of its slots' inputs (gss_run_impl.h: h2d): 16-byte vector loads, four in
    flight per lane; the tail bytes (and unaligned buffers) byte by byte */
 __global__ __launch_bounds__(256) void upload_kernel(const uint4 *__restrict__ src,
                                                      uint4 *__restrict__ dst, size_t n16,

@@ -16,7 +16,7 @@ struct RunEnv {
     const char *proof = nullptr, *prover = nullptr, *spec_cus = nullptr, *render_rest = nullptr;
 };
 
-/* every getenv of a run (GSS_RUN_TRACE apart: cached per process, gss_run.hip: trace_on) */
+/* every getenv of a run (GSS_RUN_TRACE apart: cached per process, gss_run_impl.h: trace_on) */
 static inline RunEnv run_env_read()
 {
     RunEnv e;

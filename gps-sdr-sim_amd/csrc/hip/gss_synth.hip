@@ -1258,7 +1258,7 @@ extern "C" const char *gss_build_info(void)
 }
 
 
-extern "C" void gss_run_pool_prewarm(int dev);    /* gss_run.hip */
+extern "C" void gss_run_pool_prewarm(int dev);    /* gss_run_pool.hip */
 extern "C" void gss_run_pool_drain(int dev);
 
 /* The tables of a handle as the host makes them, once per process (the C/A codes alone take

@@ -15,7 +15,7 @@ re-initialises the slot (gpssim.c:1615-1626).  So every rank plans its own windo
 
 Steps 1-2 cost the same on every rank; step 3 is the carrier-only walk, the one serial piece, and
 each rank walks only its own window.  With a walker (plan_window(walker=...)) step 3 is the chain
-run ahead (gss_run.hip chain_upfront_spec): per 4,096 blocks, the rows' starts from the exact
+run ahead (gss_run_plan.hip chain_upfront_spec): per 4,096 blocks, the rows' starts from the exact
 carriers at the chunk's first block (gss_carr_chain_starts), every row's segments walked from
 guesses -- on the GPU (device_walker: gss_spec_device) or the host (host_walker: gss_spec_host)
 -- and the exact chain from those walks (gss_carr_chain_spec), which takes one partial cycle per
@@ -33,7 +33,7 @@ from . import (ANCHOR_DTYPE, MAXCH, SPEC_DTYPE, SPEC_IN_DTYPE, Scenario, carr_an
                carr_chain, carr_chain_anchored, carr_chain_guess, carr_chain_linked,
                carr_chain_spec, carr_line_end, spec_host, spec_links)
 
-SPEC_CHUNK = 4096                # blocks per run-ahead chunk (gss_run.hip chain_upfront_spec)
+SPEC_CHUNK = 4096                # blocks per run-ahead chunk (gss_run_plan.hip chain_upfront_spec)
 
 
 

@@ -1,8 +1,9 @@
 """The one build of gss_run on the CPU fakes (tests/helpers: fake_hip, fake_dev.cpp) for the tests
 that drive it with a program of tests/helpers (run_fake.cpp, impair_fake.cpp, jam_fake.cpp,
 echo_fake.cpp, fir_fake.cpp).  What does not depend on the program (the host plane, cli_args,
-gss_run.hip compiled as C++, fake_hip and fake_dev) is compiled once per pytest session and
-kept here; a program adds its own object, and its -DNO_LAUNCH twin where it has one."""
+gss_run.hip, gss_run_plan.hip and gss_run_pool.hip compiled as C++, fake_hip and fake_dev) is
+compiled once per pytest session and kept here; a program adds its own object, and its
+-DNO_LAUNCH twin where it has one."""
 import os
 import shutil
 import subprocess
@@ -35,7 +36,12 @@ def common_objects(tmp_path_factory):
         for s in srcs:
             objs.append(os.path.join(d, os.path.basename(s)[:-2] + ".o"))
             subprocess.run(["gcc"] + CF + ["-c", s, "-o", objs[-1]], check=True)
-        for s, extra in ((os.path.join(csrc, "hip", "gss_run.hip"), ["-x", "c++"]),
+        # the driver's three translation units, each compiled on its own as the library's are
+        # (GSS_RUN_SEPARATE: gss_run.hip alone would take the other two in)
+        hip_cxx = ["-x", "c++", "-DGSS_RUN_SEPARATE"]
+        for s, extra in ((os.path.join(csrc, "hip", "gss_run.hip"), hip_cxx),
+                         (os.path.join(csrc, "hip", "gss_run_plan.hip"), hip_cxx),
+                         (os.path.join(csrc, "hip", "gss_run_pool.hip"), hip_cxx),
                          (os.path.join(HELPERS, "fake_hip", "fake_hip.cpp"), []),
                          (os.path.join(HELPERS, "fake_dev.cpp"), [])):
             objs.append(os.path.join(d, os.path.basename(s).rsplit(".", 1)[0] + ".o"))

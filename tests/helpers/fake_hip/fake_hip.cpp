@@ -95,14 +95,51 @@ hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t a, int dev)
     return hipSuccess;
 }
 hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi) { *lo = 0; *hi = -1; return hipSuccess; }
-hipError_t hipMalloc(void **p, size_t n)
+static std::mutex counts_mu;
+static fake_hip_counts_t counts;
+template <class F> static void count(F f)
+{
+    std::lock_guard<std::mutex> lk(counts_mu);
+    f(counts);
+}
+void fake_hip_counts_take(fake_hip_counts_t *out)
+{
+    std::lock_guard<std::mutex> lk(counts_mu);
+    *out = counts;
+    counts = fake_hip_counts_t{};
+}
+
+static hipError_t fake_alloc(void **p, size_t n)
 {
     *p = aligned_alloc(256, (n + 255) & ~(size_t)255);
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
-hipError_t hipFree(void *p) { free(p); return hipSuccess; }
-hipError_t hipHostMalloc(void **p, size_t n, unsigned flags) { (void)flags; return hipMalloc(p, n); }
-hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
+hipError_t hipMalloc(void **p, size_t n)
+{
+    count([](fake_hip_counts_t &c) { c.malloc++; });
+    return fake_alloc(p, n);
+}
+hipError_t hipFree(void *p)
+{
+    count([](fake_hip_counts_t &c) { c.free++; });
+    free(p);
+    return hipSuccess;
+}
+hipError_t hipHostMalloc(void **p, size_t n, unsigned flags)
+{
+    (void)flags;
+    count([n](fake_hip_counts_t &c) {
+        c.host_malloc++;
+        c.host_malloc_max = n > c.host_malloc_max ? n : c.host_malloc_max;
+    });
+    return fake_alloc(p, n);
+}
+hipError_t hipHostFree(void *p)
+{
+    count([](fake_hip_counts_t &c) { c.host_free++; });
+    free(p);
+    return hipSuccess;
+}
 hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind k)
 {
     (void)k;
@@ -123,6 +160,7 @@ hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t s)
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned flags)
 {
     (void)flags;
+    count([](fake_hip_counts_t &c) { c.stream_create++; });
     *s = new fake_stream();
     return hipSuccess;
 }
@@ -138,6 +176,7 @@ hipError_t hipExtStreamCreateWithCUMask(hipStream_t *s, uint32_t n, const uint32
 }
 hipError_t hipStreamDestroy(hipStream_t s)
 {
+    count([](fake_hip_counts_t &c) { c.stream_destroy++; });
     if (s) {
         hipStreamSynchronize(s);
         delete s;
@@ -151,9 +190,19 @@ hipError_t hipStreamSynchronize(hipStream_t s)
     f->wait(upto);
     return hipSuccess;
 }
-hipError_t hipEventCreate(hipEvent_t *e) { *e = new fake_event(); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t *e)
+{
+    count([](fake_hip_counts_t &c) { c.event_create++; });
+    *e = new fake_event();
+    return hipSuccess;
+}
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags) { (void)flags; return hipEventCreate(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e)
+{
+    count([](fake_hip_counts_t &c) { c.event_destroy++; });
+    delete e;
+    return hipSuccess;
+}
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
 {
     uint64_t g;

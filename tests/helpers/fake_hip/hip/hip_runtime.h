@@ -68,6 +68,15 @@ hipError_t hipEventSynchronize(hipEvent_t e);
 hipError_t hipEventQuery(hipEvent_t e);
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b);
 
+/* calls that allocate or release since the previous fake_hip_counts_take (the pools' business:
+   run_fake prints them per case); host_malloc_max: the largest hipHostMalloc request, bytes */
+typedef struct fake_hip_counts {
+    long malloc, host_malloc, free, host_free;
+    long stream_create, stream_destroy, event_create, event_destroy;
+    size_t host_malloc_max;
+} fake_hip_counts_t;
+void fake_hip_counts_take(fake_hip_counts_t *out);
+
 #ifdef __cplusplus
 /* device work (a fake kernel) queued on stream s, run by its thread in stream order */
 void fake_enqueue(hipStream_t s, std::function<void()> fn);

@@ -1,7 +1,8 @@
 /*
- * run_fake.cpp — gss_run itself (csrc/hip/gss_run.hip: its planner, rows and prover threads, slot
- * state machine, output-buffer pool, uploads, streams and events) on the CPU, for the sanitizers
- * (tools/sanitize.sh: -fsanitize=thread, -fsanitize=address,undefined).  gss_run.hip is built
+ * run_fake.cpp — gss_run itself (csrc/hip/gss_run.hip: the main thread and the slot state machine;
+ * gss_run_plan.hip: its planner, rows and prover threads; gss_run_pool.hip: the buffer and stream
+ * pools) on the CPU, for the sanitizers (tools/sanitize.sh: -fsanitize=thread,
+ * -fsanitize=address,undefined).  The three files are built
  * unchanged against the fake HIP runtime of tests/helpers/fake_hip (streams drained by their own
  * threads), with the device functions of tests/helpers/fake_dev.cpp (host walks, host proofs, a
  * render that writes each block's fingerprint).  Every byte the sink receives is checked
@@ -24,10 +25,11 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include <hip/hip_runtime.h>                     /* the fake's: fake_hip_counts_take */
 #include "gpssim_amd.h"
 #include "fake_dev.h"
 
-extern "C" void gss_run_pool_drain(int dev);      /* gss_run.hip: the pooled slot buffers */
+extern "C" void gss_run_pool_drain(int dev);      /* gss_run_pool.hip: the pooled buffers */
 
 static const char *g_nav;
 static double g_secs = 70.0;
@@ -142,6 +144,18 @@ static void set_env(const Mode &m)
 
 static int fails = 0;
 
+/* what the case just run allocated, created and released (the fake runtime's counters since the
+   previous line): the pools' behaviour, which must not depend on how the driver is laid out */
+static fake_hip_counts_t counts(const char *what)
+{
+    fake_hip_counts_t c;
+    fake_hip_counts_take(&c);
+    printf("counts %s: malloc %ld free %ld host_malloc %ld host_free %ld streams +%ld -%ld "
+           "events +%ld -%ld\n", what, c.malloc, c.free, c.host_malloc, c.host_free,
+           c.stream_create, c.stream_destroy, c.event_create, c.event_destroy);
+    return c;
+}
+
 static void check(const char *what, int rc, const Sink &k, int64_t first, int64_t want_blocks)
 {
     const bool ok = rc == 0 && k.bad == 0 && k.blocks == want_blocks &&
@@ -152,6 +166,7 @@ static void check(const char *what, int rc, const Sink &k, int64_t first, int64_
             printf("  error: %s\n", gss_last_error());
         fails++;
     }
+    counts(what);
 }
 
 struct Baton {
@@ -284,8 +299,16 @@ int main(int argc, char **argv)
         const int64_t mid = nblk / 2 + 3;
         Sink k{bb, 0};
         int rc = gss_run(d, s, 0, mid, batch, 4, sink, &k);
+        counts("two runs on one handle, the first");
         if (!rc)
             rc = gss_run(d, s, mid, -1, batch, 4, sink, &k);
+        /* the second run takes its streams and its slots' pinned output buffers from the pools */
+        const fake_hip_counts_t c = counts("two runs on one handle, the second");
+        if (!rc && (c.stream_create != 0 || c.host_malloc_max >= bb * (size_t)batch)) {
+            printf("  the second run created %ld streams and pinned up to %zu B\n",
+                   c.stream_create, c.host_malloc_max);
+            rc = 1;
+        }
         check("two runs on one handle", rc, k, 0, nblk);
         gss_scn_close(s);
     }
@@ -351,6 +374,7 @@ int main(int argc, char **argv)
         printf("%-44s rc %d blocks %ld %s\n", "sink stops the run", rc, k.blocks,
                ok ? "ok" : "FAIL");
         fails += !ok;
+        counts("sink stops the run");
         gss_scn_close(s);
     }
     gss_run_pool_drain(-1);

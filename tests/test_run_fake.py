@@ -1,5 +1,5 @@
-"""gss_run (csrc/hip/gss_run.hip and its gss_run_modes.h, as shipped) on the CPU fake of the HIP
-runtime.
+"""gss_run (csrc/hip/gss_run.hip, gss_run_plan.hip and gss_run_pool.hip with their headers, as
+shipped) on the CPU fake of the HIP runtime.
 
 tests/helpers/fake_hip stands in for the HIP calls gss_run makes (streams drained by worker
 threads, events as generation counters), tests/helpers/fake_dev.cpp for its device functions

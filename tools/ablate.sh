@@ -13,7 +13,9 @@ mkdir -p _var/$name/obj
 HIPCC=/opt/rocm/bin/hipcc
 F="-O3 -fPIC -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Iinclude -Wno-unused-result -mllvm -amdgpu-mfma-vgpr-form=1 $flags"
 $HIPCC $F -c ${SYNTH_SRC:-gps-sdr-sim_amd/csrc/hip/gss_synth.hip} -o _var/$name/obj/gss_synth.o
-$HIPCC $F -c gps-sdr-sim_amd/csrc/hip/gss_run.hip -o _var/$name/obj/gss_run.o
+for f in gss_run gss_run_plan gss_run_pool; do
+    $HIPCC $F -c gps-sdr-sim_amd/csrc/hip/$f.hip -o _var/$name/obj/$f.o
+done
 $HIPCC $F -c gps-sdr-sim_amd/csrc/hip/gss_producers.hip -o _var/$name/obj/gss_producers.o
 $HIPCC $F -c gps-sdr-sim_amd/csrc/hip/gss_proof.hip -o _var/$name/obj/gss_proof.o
 $HIPCC $F -c gps-sdr-sim_amd/csrc/hip/gss_impair.hip -o _var/$name/obj/gss_impair.o
@@ -28,5 +30,6 @@ if [ -n "$HOSTFLAGS" ]; then          # the host proof must agree with the kerne
 fi
 $HIPCC -shared -fPIC --offload-arch=gfx950 -Wl,--version-script=gps-sdr-sim_amd/exports.map \
     -o _var/$name/libgpssim_amd.so $HOSTOBJ \
-    _var/$name/obj/gss_synth.o _var/$name/obj/gss_run.o _var/$name/obj/gss_producers.o \
+    _var/$name/obj/gss_synth.o _var/$name/obj/gss_run.o _var/$name/obj/gss_run_plan.o \
+    _var/$name/obj/gss_run_pool.o _var/$name/obj/gss_producers.o \
     _var/$name/obj/gss_proof.o _var/$name/obj/gss_impair.o -lm -lpthread

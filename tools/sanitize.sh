@@ -1,9 +1,9 @@
 #!/bin/bash
 # The host side under the sanitizers (CPU only), once with -fsanitize=thread and
 # once with -fsanitize=address,undefined; any sanitizer report, row or byte mismatch fails.
-#  * gss_run itself (gps-sdr-sim_amd/csrc/hip/gss_run.hip with its gss_run_modes.h, as shipped: its
-#    planner, rows and prover threads, slot state machine, buffer pool, uploads, streams and
-#    events) built against
+#  * gss_run itself (gps-sdr-sim_amd/csrc/hip/gss_run.hip, gss_run_plan.hip and gss_run_pool.hip
+#    with their headers, as shipped: its planner, rows and prover threads, slot state machine,
+#    buffer pool, uploads, streams and events) built against
 #    the CPU stand-in of the HIP runtime (tests/helpers/fake_hip) and the CPU fakes of its device
 #    functions (tests/helpers/fake_dev.cpp), driven through every mode of the run by
 #    tests/helpers/run_fake.cpp, which checks every byte the sink gets against independently
@@ -24,6 +24,7 @@ SRC="gps-sdr-sim_amd/csrc/host/*.c gps-sdr-sim_amd/csrc/cli/cli_args.c tests/hel
 CF="-O1 -g -fno-omit-frame-pointer -ffp-contract=off -fno-fast-math -D_FILE_OFFSET_BITS=64 -Iinclude"
 NAV=tests/golden/data/brdc3540.14n
 rc=0
+RUN="gss_run gss_run_plan gss_run_pool"              # the driver's translation units
 FK="tests/helpers/fake_hip/fake_hip.cpp tests/helpers/fake_dev.cpp tests/helpers/run_fake.cpp"
 # one object per source, built in parallel (each a background job, every status checked)
 build() {  # san dir
@@ -32,8 +33,10 @@ build() {  # san dir
              tests/helpers/run_harness.c; do
         gcc $CF -fsanitize=$san -c $f -o $d/$(basename ${f%.c}).o & pids+=($!)
     done
-    g++ -std=c++17 $CF -Itests/helpers -Itests/helpers/fake_hip -fsanitize=$san -x c++ \
-        -c gps-sdr-sim_amd/csrc/hip/gss_run.hip -o $d/gss_run.o & pids+=($!)
+    for f in $RUN; do
+        g++ -std=c++17 $CF -Itests/helpers -Itests/helpers/fake_hip -fsanitize=$san -DGSS_RUN_SEPARATE -x c++ \
+            -c gps-sdr-sim_amd/csrc/hip/$f.hip -o $d/$f.o & pids+=($!)
+    done
     for f in $FK; do
         g++ -std=c++17 $CF -Itests/helpers -Itests/helpers/fake_hip -fsanitize=$san -c $f \
             -o $d/$(basename ${f%.cpp}).o & pids+=($!)
@@ -49,10 +52,10 @@ for san in thread address,undefined; do
     rm -rf $d
     mkdir -p $d
     build $san $d || exit 1
-    host_objs=$(ls $d/*.o | grep -v -e '/gss_run.o$' -e '/fake_hip.o$' -e '/fake_dev.o$' \
+    host_objs=$(ls $d/*.o | grep -v -e '/gss_run[a-z_]*.o$' -e '/fake_hip.o$' -e '/fake_dev.o$' \
                 -e '/run_fake.o$' -e '/run_harness.o$')
-    g++ -fsanitize=$san -o $d/run_fake $host_objs $d/gss_run.o $d/fake_hip.o $d/fake_dev.o \
-        $d/run_fake.o -lm -lpthread || exit 1
+    g++ -fsanitize=$san -o $d/run_fake $host_objs $d/gss_run.o $d/gss_run_plan.o \
+        $d/gss_run_pool.o $d/fake_hip.o $d/fake_dev.o $d/run_fake.o -lm -lpthread || exit 1
     IFS=';' read -ra fargs <<< "${FAKE_ARGS:-70 64 1;40 16 8;300 512 1}"
     for args in "${fargs[@]}"; do
         log=$OUT/gss_run_${tag}_$(echo $args | tr ' ' _).log
