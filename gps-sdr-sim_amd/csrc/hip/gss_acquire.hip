@@ -384,7 +384,8 @@ extern "C" int gss_acquire_device(gss_dev *d, const gss_acq_t *a, const void *d_
     A.n_prn = dm.n_prn; A.fs = a->fs_hz; A.bin_hz = a->bin_hz; A.fmt = a->fmt;
     A.qshift = a->qshift; A.N = dm.N;
     A.Lpad = (dm.L + ACQ_LC - 1) / ACQ_LC * ACQ_LC;
-    /* the correlator reads up to tau tile + chunk + 36 bytes past the last window's start */
+    /* the correlator reads ACQ_SEGW dwords (tau tile + chunk + 36 bytes) of a plane from the
+       dword at or below byte tau_blk + m L + i0, which lies below M L + T */
     A.Npad = ((int64_t)A.M * dm.L + dm.T + ACQ_TB + ACQ_LC + 64 + 1023) / 1024 * 1024;
     for (int p = 0; p < dm.n_prn; p++)
         A.prn[p] = (uint8_t)dm.prn[p];

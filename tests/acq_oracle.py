@@ -51,9 +51,11 @@ def planes(xi, xq, fs, df, K, sh):
     return np.array(qi), np.array(qq)
 
 
-def replicas(prns, fs, n):
+def replicas(prns, fs, n, start=0):
+    """+1 / -1 [len(prns), n]: replica samples start .. start + n - 1 (a negative index is the
+    code continued backwards: floor division)"""
     ca = G.ca_table()
-    chip = (np.arange(n, dtype=np.int64) * 1023000 // fs) % 1023
+    chip = (np.arange(start, start + n, dtype=np.int64) * 1023000 // fs) % 1023
     out = np.empty((len(prns), n))
     for j, p in enumerate(prns):
         bit = (ca[p - 1][chip >> 5] >> (chip & 31).astype(np.uint32)) & 1
@@ -120,6 +122,149 @@ def random_samples(fs, coh_ms, M, fmt, seed, extreme=False):
     if fmt == 8:
         return rng.integers(-128, 128, 2 * N).astype(np.int8).view(np.uint8)
     return rng.integers(0, 256, (N + 3) // 4 + 1).astype(np.uint8)
+
+
+# ---- edge shapes, planted peaks and ties -----------------------------------------------------
+# The correlator loads a window's q segment from the aligned dword below byte
+# tau_blk + m L + i0 (tau_blk a multiple of 128, i0 of 1024) and adds the remainder shb to every
+# later offset: shb != 0 needs L % 4 != 0, which no row of SHAPES has.
+_ALL = tuple(range(1, 33))
+EDGE_SHAPES = [
+    (65001, 1, 3, 1, 500, (1, 32)),               # L = 65, T = 66: shb = 0, 1, 2; T below a tile
+    (1023000, 1, 4, 1, 500, _ALL[:17]),           # L = T = 1023: shb = 0, 3, 2, 1; slot 16 alone
+                                                  # in the second slot tile; one chunk of 1023
+    (1025000, 1, 2, 0, 500, _ALL[:16]),           # L = T = 1025: a second chunk of one sample;
+                                                  # 16 slots exactly; one bin; 8 tau tiles + 1
+    (128000, 1, 2, 2, 500, (3,)),                 # L = T = 128: one full tau tile; one PRN
+    (129000, 1, 1, 1, 500, (3, 9)),               # L = T = 129: one phase in a second tile
+    (6000, 1, 1000, 1, 500, (1, 2)),              # L = T = 6: the smallest T (2 E + 1 = 5), the
+                                                  # largest n_coh, one mostly-zero k-block
+    (2047500, 2, 2, 1, 250, (1, 2, 3)),           # L = 4095, T = 2048: odd L over four chunks
+                                                  # (the last of 1023); coh_ms 2; 16 tau tiles
+    (6000, 1, 2, 130, 10, _ALL),                  # 261 bins: the peak kernel's second pass
+    (1024000, 1, 2, 0, 500, (7,)),                # L = T = 1024: one full chunk, no zero padding
+                                                  # of the replica; 8 tau tiles exactly
+]
+BINS261 = 7                                       # the row of EDGE_SHAPES with more than 256 bins
+# the seed of a row's SC16 random input; BINS261's is chosen so that the peaks of the automatic
+# shift lie on both sides of bin index 256 (checked by check_precondition)
+_EDGE_SEED = {BINS261: 103}
+
+PLANT_SHAPE = EDGE_SHAPES[1]
+PLANT_TAUS = (0, 1, 3, 1019, 1021, 1022)          # 0, 1, E, T - 1 - E, T - 2, T - 1: the floor's
+                                                  # excluded zone wraps at both ends
+
+
+def planted(shape, taus, seed, amp=1000, noise=40):
+    """SC16 bytes: the replica of the shape's j-th PRN delayed by taus[j] samples at amplitude amp
+    on I, plus uniform noise of +- noise on I and Q"""
+    fs, coh, M, _, _, prns = shape
+    N = sizes(fs, coh, M)[2]
+    v = np.random.default_rng(seed).integers(-noise, noise + 1, (N, 2))
+    for p, tau in zip(sorted(prns), taus):
+        v[:, 0] += amp * replicas([p], fs, N, start=-tau)[0].astype(np.int64)
+    return v.astype("<i2").view(np.uint8).reshape(-1)
+
+
+def half_rate(shape, tau, seed, amp=1000, noise=40):
+    """SC16 bytes: the first PRN's replica delayed by tau, times (-1)^n.  With bin_hz = fs / 2
+    the carrier steps of bins -1 and +1 are both 2^31, which undoes the alternation."""
+    fs, coh, M, _, _, prns = shape
+    N = sizes(fs, coh, M)[2]
+    v = np.random.default_rng(seed).integers(-noise, noise + 1, (N, 2))
+    sign = 1 - 2 * (np.arange(N) & 1)
+    v[:, 0] += amp * sign * replicas([sorted(prns)[0]], fs, N, start=-tau)[0].astype(np.int64)
+    return v.astype("<i2").view(np.uint8).reshape(-1)
+
+
+def constant(shape):
+    """SC16 bytes: xI = 1, xQ = 0"""
+    N = sizes(*shape[:3])[2]
+    return np.tile(np.array([1, 0], "<i2"), N).view(np.uint8)
+
+
+def edge_cases():
+    """(name, shape, fmt, (kind, seed), qshift) for every row of EDGE_SHAPES: SC16 at shift 0, 7
+    and automatic and the extreme input; SC08 and SC01 at the automatic shift and at 0 (SC08 at
+    0: already-quantised samples times 250, every sum saturated)"""
+    out = []
+    for si, s in enumerate(EDGE_SHAPES):
+        for q in (0, 7, -1):
+            out.append((f"e{si}-q{q}", s, 16, ("rand", _EDGE_SEED.get(si, 100 + si)), q))
+        out.append((f"e{si}-extreme", s, 16, ("extreme", 150 + si), -1))
+        for fmt in (8, 1):
+            for q in (-1, 0):
+                out.append((f"e{si}-b{fmt}-q{q}", s, fmt, ("rand", 120 + si), q))
+    return out
+
+
+# Ties.  bin_hz = fs makes every carrier step 0 mod 2^32 (all bins of a PRN identical);
+# bin_hz = fs / 2 with K = 1 makes bins -1 and +1 identical; a constant input with one bin makes
+# a whole row equal and non-zero.  The sine table is not symmetric: mirror bins do not tie.
+SPECIAL_CASES = [
+    ("planted", PLANT_SHAPE, 16, ("planted", 5), -1),
+    ("alias-64", (64000, 1, 2, 2, 64000, (1, 32)), 16, ("rand", 200), -1),
+    ("alias-261", (6000, 1, 2, 130, 6000, _ALL), 16, ("rand", 201), -1),
+    ("half-rate", (64000, 1, 2, 1, 32000, (1, 32)), 16, ("half", 202), -1),
+    ("const-64", (64000, 1, 2, 0, 500, (1, 32)), 16, ("const", 0), 0),
+    ("const-1025", (1025000, 1, 2, 0, 500, (1, 17, 32)), 16, ("const", 0), 0),
+    ("zero", SHAPES[0], 16, ("zero", 0), 0),
+]
+HALF_TAU = 37
+
+
+def case_data(case):
+    """the input bytes of a case of edge_cases() or SPECIAL_CASES"""
+    _, shape, fmt, (kind, seed), _ = case
+    if kind == "planted":
+        return planted(shape, PLANT_TAUS, seed)
+    if kind == "half":
+        return half_rate(shape, HALF_TAU, seed)
+    if kind == "const":
+        return constant(shape)
+    if kind == "zero":
+        return np.zeros(4 * sizes(*shape[:3])[2], np.uint8)
+    return random_samples(shape[0], shape[1], shape[2], fmt, seed, extreme=kind == "extreme")
+
+
+_answers = {}
+
+
+def answer(case):
+    """acquire() over a case's input, computed once per process: the host tests and both GPU
+    paths share it.  What the case is for is checked here, on the oracle's own answer."""
+    name, shape, fmt, _, qshift = case
+    if name not in _answers:
+        fs, coh, M, K, df, prns = shape
+        _answers[name] = acquire(case_data(case), fs, fmt, coh, M, K, df, prns, qshift)
+        check_precondition(case, *_answers[name][:2])
+    return _answers[name]
+
+
+def check_precondition(case, peaks, grid):
+    """does the oracle's answer show the edge the case was built for?"""
+    name, shape, _, (kind, _), _ = case
+    K, T = shape[3], grid.shape[2]
+    if kind == "planted":                          # every planted PRN peaks where it was put
+        n = len(PLANT_TAUS)
+        assert tuple(peaks["tau"][:n]) == PLANT_TAUS and (peaks["bin"][:n] == 0).all(), peaks
+    elif name.startswith("alias"):                 # identical bins: bin -K, the first maximum
+        assert (grid == grid[:, :1, :]).all() and grid.any()
+        assert (peaks["bin"] == -K).all()
+        assert (peaks["tau"] == grid[:, 0, :].argmax(axis=1)).all()
+    elif kind == "half":                           # the peak in the tied pair: the lower bin
+        assert np.array_equal(grid[:, 0], grid[:, 2])
+        assert peaks["bin"][0] == -1 and peaks["tau"][0] == HALF_TAU, peaks
+        assert grid[0, 0].max() > grid[0, 1].max()
+    elif kind == "const":                          # one equal non-zero row per PRN: tau 0
+        assert (grid == grid[:, :, :1]).all() and grid.all()
+        assert (peaks["tau"] == 0).all() and (peaks["bin"] == 0).all()
+        assert (peaks["floor_cnt"] == T - 2 * sizes(*shape[:3])[3] - 1).all()
+    elif kind == "zero":
+        assert not grid.any() and (peaks["tau"] == 0).all() and (peaks["bin"] == -K).all()
+    elif name == f"e{BINS261}-q-1":                # peaks in both passes of the candidate loop
+        idx = peaks["bin"] + K
+        assert (idx >= 256).any() and (idx < 256).any(), idx
 
 
 # ---- the physical test's inputs --------------------------------------------------------------

@@ -77,6 +77,38 @@ def test_ties_take_the_lowest_bin_then_tau():
     assert (peaks["peak"] == 0).all() and (peaks["floor_sum"] == 0).all()
 
 
+def check_case(case):
+    """gss_acquire_host over a case of acq_oracle against the oracle's shared answer (which
+    holds the case's precondition), with and without the grid"""
+    _, shape, fmt, _, qshift = case
+    want_p, want_g, want_sh = O.answer(case)
+    data = O.case_data(case)
+    peaks, grid, sh = G.acquire_host(acq_of(shape, fmt, qshift), data, want_grid=True)
+    assert sh == want_sh
+    assert np.array_equal(grid, want_g), np.argwhere(grid != want_g)[:8]
+    assert np.array_equal(peaks, want_p), (peaks, want_p)
+    nogrid, none, sh2 = G.acquire_host(acq_of(shape, fmt, qshift), data)
+    assert none is None and sh2 == sh and np.array_equal(nogrid, want_p)
+
+
+EDGE_CASES = O.edge_cases()
+
+
+@pytest.mark.parametrize("case", EDGE_CASES, ids=[c[0] for c in EDGE_CASES])
+def test_host_equals_oracle_edge_shapes(case):
+    """window lengths that are no multiple of 4, exact and just-exceeded tau tiles and chunks,
+    16 and 17 PRNs, one bin and 261 bins, the largest n_coh: every format and shift"""
+    check_case(case)
+
+
+@pytest.mark.parametrize("case", O.SPECIAL_CASES, ids=[c[0] for c in O.SPECIAL_CASES])
+def test_host_planted_peaks_and_ties(case):
+    """peaks planted at both ends of the code period (the floor's zone wraps), and inputs whose
+    cells tie at a non-zero value across bins, across a pair of bins and along a whole row: the
+    lowest bin, then the lowest code phase"""
+    check_case(case)
+
+
 def test_argument_errors():
     ok = dict(fs_hz=1000000, fmt=16, coh_ms=1, n_coh=2, bin_hz=500, n_half=2, qshift=-1)
     x = np.zeros(8 * 4000, np.uint8)

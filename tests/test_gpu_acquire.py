@@ -1,6 +1,7 @@
 """The acquisition search on the GPU (csrc/hip/gss_acquire.hip): Device.acquire against the numpy
-restatement of tests/acq_oracle.py, bit for bit, on the matrix-core path and the VALU path; the
-scratch regrowing between calls; and end to end: a noisy run's first block holds the satellites
+restatement of tests/acq_oracle.py, bit for bit, on the matrix-core path and the VALU path, at
+the oracle's edge shapes (odd window lengths, tile and chunk edges), planted peaks and ties too;
+the scratch regrowing between calls; and end to end: a noisy run's first block holds the satellites
 its channel rows describe, at the level the noise option asked for."""
 import numpy as np
 import pytest
@@ -77,7 +78,7 @@ def cases():
         for fmt in (8, 1):
             out.append((f"s{si}-b{fmt}", SHAPES[si], fmt, ("rand", 20 + si), -1))
     out.append(("big", BIG, 16, ("rand", 99), -1))
-    return out
+    return out + O.edge_cases() + O.SPECIAL_CASES
 
 
 CASES = cases()
@@ -86,9 +87,9 @@ CASES = cases()
 @pytest.mark.parametrize("path", ["mfma", "valu"])
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_device_equals_oracle(dev, monkeypatch, case, path):
-    name, shape, fmt, (kind, seed), qshift = case
-    data = random_samples(shape[0], shape[1], shape[2], fmt, seed, extreme=kind == "extreme")
-    wp, wg, wsh = want(name, shape, fmt, data, qshift)
+    name, shape, fmt, _, qshift = case
+    data = O.case_data(case)
+    wp, wg, wsh = O.answer(case)
     if path == "valu":
         monkeypatch.setenv("GSS_ACQ_PATH", "valu")
     else:
@@ -116,6 +117,32 @@ def test_scratch_regrows(dev, monkeypatch, path):
         assert sh == wsh and np.array_equal(peaks, wp), tag
         peaks, grid, sh = on_device(dev, acq_of(s), data)
         assert np.array_equal(grid, wg) and np.array_equal(peaks, wp), tag
+
+
+def edge_case(si, tag="q-1"):
+    return next(c for c in O.edge_cases() if c[0] == f"e{si}-{tag}")
+
+
+@pytest.mark.parametrize("path", ["mfma", "valu"])
+def test_scratch_regrows_at_odd_lengths(monkeypatch, path):
+    """a new handle goes from L = 65 to L = 1023 to L = 4095: the padded plane and replica
+    lengths grow while the windows start off a dword boundary"""
+    if path == "valu":
+        monkeypatch.setenv("GSS_ACQ_PATH", "valu")
+    else:
+        monkeypatch.delenv("GSS_ACQ_PATH", raising=False)
+    d = G.Device(0)
+    try:
+        for si in (0, 1, 6):
+            case = edge_case(si)
+            wp, wg, wsh = O.answer(case)
+            data = O.case_data(case)
+            peaks, none, sh = on_device(d, acq_of(case[1]), data, want_grid=False)
+            assert sh == wsh and np.array_equal(peaks, wp), si
+            peaks, grid, sh = on_device(d, acq_of(case[1]), data)
+            assert np.array_equal(grid, wg) and np.array_equal(peaks, wp), si
+    finally:
+        d.close()
 
 
 def test_each_handle_owns_its_scratch(monkeypatch):
@@ -175,6 +202,15 @@ def test_from_host_buffers(dev):
     assert sh == wsh and np.array_equal(grid, wg) and np.array_equal(peaks, wp)
 
 
+def test_from_host_buffers_odd_length(dev, monkeypatch):
+    """gss_acquire's own upload and download at L = T = 1023 with 17 PRNs"""
+    monkeypatch.delenv("GSS_ACQ_PATH", raising=False)
+    case = edge_case(1)
+    wp, wg, wsh = O.answer(case)
+    peaks, grid, sh = dev.acquire_from_host(acq_of(case[1]), O.case_data(case), want_grid=True)
+    assert sh == wsh and np.array_equal(grid, wg) and np.array_equal(peaks, wp)
+
+
 @pytest.mark.parametrize("fmt", [16, 8, 1])
 def test_end_to_end(dev, fmt):
     """gss_run with noise at 50 dB-Hz, the search over the run's first block on the device: the
@@ -218,3 +254,27 @@ def test_cli_on_the_gpu(dev, tmp_path):
     _, want, _ = G.acquire_host(G.Acq(O.PHYS_FS, 16, 1, 8, 500, 10, -1, [1, 2, 3, 17, 28]),
                                 data, want_grid=True)
     assert np.array_equal(np.fromfile(g, np.uint64).reshape(want.shape), want)
+
+
+def test_cli_at_an_odd_window_length(dev, tmp_path):
+    """gps-sdr-acq at 1.023 MS/s (L = T = 1023) over the planted peaks: the GPU search prints
+    what --host prints, the planted code phases among them, and writes the host's grid"""
+    import subprocess
+    case = O.SPECIAL_CASES[0]
+    fs, coh, M, K, df, prns = case[1]
+    assert case[0] == "planted" and prns == tuple(range(1, 18))
+    wp, wg, _ = O.answer(case)
+    f, g = tmp_path / "planted.bin", tmp_path / "grid.bin"
+    O.case_data(case).tofile(f)
+    args = [G.ACQ_CLI_PATH, "-f", str(f), "-s", str(fs), f"--ncoh={M}", f"--fmax={K * df}",
+            "--prn=1-17"]
+    gpu = subprocess.run(args + [f"--grid={g}"], capture_output=True, text=True)
+    host = subprocess.run(args + ["--host"], capture_output=True, text=True)
+    assert gpu.returncode == 0 and host.returncode == 0, gpu.stderr + host.stderr
+    assert gpu.stdout == host.stdout
+    rows = [ln.split() for ln in gpu.stdout.splitlines()]
+    assert [(int(r[0]), int(r[2]), int(r[3])) for r in rows] == \
+        [(int(p["prn"]), int(p["tau"]), int(p["bin"]) * df) for p in wp]
+    _, hg, _ = G.acquire_host(acq_of(case[1]), O.case_data(case), want_grid=True)
+    assert np.array_equal(np.fromfile(g, np.uint64).reshape(hg.shape), hg)
+    assert np.array_equal(hg, wg)
